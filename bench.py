@@ -9,14 +9,23 @@ check, flip, TimeLimit 1000, auto-reset -- and every per-env output of the
 ply written to HBM (int32[24] obs, reward, terminated, truncated, compact
 legal set, actions).  The timed path is k_rollout: P plies per launch with
 the env record in VGPRs, each ply's outputs streamed to [P][B] rollout
-buffers (K steps = ceil(K/P) launches).  The per-ply API kernel k_step is
-measured beside it (eager and hipGraph-replayed).  N GPUs = N processes,
+buffers (K steps = ceil(K/P) launches).  N GPUs = N processes,
 each owning a contiguous shard of global env ids (weak scaling): under
 torchrun (WORLD_SIZE set) the bench is one rank and checks that the world
 size equals --gpus; run plainly with --gpus N > 1 it starts the N ranks
 itself (torch.distributed.run, 127.0.0.1) before touching the GPU.  The
 timed region ends with every rank's episode totals (one kernel) and, at
 N > 1, the RCCL all-gather of them.
+
+A plain run sets up, ramps the device, warms up, times the K steps and prints
+the line.  --full adds every other leg (each reported beside the headline,
+null in a plain run's line): the CPU baseline, the checker leg (the C oracle
+replaying the timed launches), the per-ply API kernel k_step (eager and
+hipGraph-replayed), the rollout without outputs, the other rules mode and
+the DQN driver.  --dump-outputs DIR writes the last timed ply's outputs of
+rank 0's shard as DIR/<name>.npy (dump_outputs): with the same arguments the
+envs, seeds and the number of plies before that ply are the same from run to
+run, so two builds can be compared output for output.
 
 Prints ONE JSON line on rank 0 (fields: DESIGN.md section 6).
 """
@@ -49,6 +58,44 @@ OUT_BYTES_PER_STEP_FULL = 118
 PORT_OVER_REFERENCE = 1.015
 # plies per launch of the untimed device ramp
 RAMP_PLIES = 1000
+# --dump-outputs: envs written per array (at most 140 B per env over all
+# arrays: 37 MB); a larger shard is sampled
+DUMP_MAX_ENVS = 262144
+
+
+def dump_outputs(path, bufs, row, totals_rows):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    ply, as <path>/<name>.npy -- row `row` (the last ply played) of every
+    [P][B] rollout buffer and the last launch's per-256-env totals rows.
+    32-bit and narrower integers are written as float32 (exact: |x| < 2^24),
+    64-bit words (legal sets, FULL4 played sub-moves) as their low and high
+    32-bit halves in float64 (<name>_lo, <name>_hi), the totals rows as
+    float64.  A shard of more than DUMP_MAX_ENVS envs is sampled: the same
+    seeded, sorted env indices every run (env_index.npy)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    out, idx = {}, None
+    for name, buf in bufs.items():
+        if buf is None:
+            continue
+        a = buf[row].cpu().numpy()
+        if a.shape[0] > DUMP_MAX_ENVS:
+            if idx is None:
+                idx = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_ENVS, replace=False))
+            a = a[idx]
+        if a.dtype.itemsize == 8:
+            u = a.view(np.uint64)
+            out[name + "_lo"] = (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+            out[name + "_hi"] = (u >> np.uint64(32)).astype(np.float64)
+        else:
+            out[name] = a.astype(np.float32)
+    out["totals_rows"] = totals_rows.cpu().numpy().astype(np.float64)
+    if idx is not None:
+        out["env_index"] = idx.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
 
 
 def launch_bytes(envs, plies, full=False):
@@ -421,7 +468,17 @@ def main():
     ap.add_argument("--parity-core-s", type=float, default=160.0,
                     help="oracle work the checker may spend per leg (host core-seconds): the whole "
                          "shard when it fits, else a prefix of >= 16,384 envs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the CPU baseline, the checker leg, "
+                         "the API kernel, the rollout without outputs, the other rules mode and the DQN "
+                         "driver (a plain run sets up, warms up, times --steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed ply's outputs of rank 0's shard "
+                         "as DIR/<name>.npy (float32 / float64; the same from run to run)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline's own work only
+        args.no_cpu_baseline = args.no_parity_check = True
+        args.api_steps = args.fused_launches = args.other_launches = args.dqn_steps = 0
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None:
@@ -495,17 +552,24 @@ def main():
     # untimed device ramp, whatever --warmup is: a cold MI355X runs its first
     # ~100 back-to-back launches of this kernel at DVFS-reduced clocks
     # (DESIGN.md section 6), so the ramp plays RAMP_PLIES-ply launches of the
-    # same kernel for at least --ramp-ms and --ramp-launches
+    # same kernel for at least --ramp-ms and --ramp-launches.  The timed env
+    # plays --ramp-launches of them (in tens); the launches that fill
+    # --ramp-ms, whose number depends on the clock, play on an env of their
+    # own, so the plies the timed env has played when the region starts -- and
+    # with them every output of the region -- are the same from run to run
     ramp_n, ramp_t0 = 0, time.perf_counter()
     if args.ramp_launches > 0:
         rbufs = bufs if P == RAMP_PLIES else env.rollout_buffers(RAMP_PLIES)
         ramp = env.rollout_launcher(RAMP_PLIES, rbufs)
+        env_fill = eng.make_env(per, first, args.seed, args.rules)
+        fill = env_fill.rollout_launcher(RAMP_PLIES, rbufs)
         while ramp_n < args.ramp_launches or (time.perf_counter() - ramp_t0) * 1e3 < args.ramp_ms:
             for _ in range(10):
-                ramp()
+                (ramp if ramp_n < args.ramp_launches else fill)()
             ramp_n += 10
             eng.sync()
-        del ramp, rbufs
+        del ramp, fill, rbufs
+        env_fill.close()
     ramp_ms = (time.perf_counter() - ramp_t0) * 1e3
 
     # the timed region's launches, pre-bound: K plies as launches of P (the
@@ -634,6 +698,12 @@ def main():
     total_steps = world * per * K
     value = total_steps / elapsed
     summary = D.summarize(totals)
+
+    # --dump-outputs: the last timed ply's outputs, copied out before any
+    # other leg plays on this env or writes these buffers (untimed)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, bufs, sizes[-1] - 1, rows_buf)
 
     if check_parity:
         # the checker's inputs, copied to the host before any other leg runs
@@ -889,6 +959,9 @@ def main():
             "steps": K,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / K * 1e3, 6),
+            # --full: the legs beside the headline ran (null below otherwise)
+            "full": args.full,
+            "dumped_outputs": dumped,
             "device_ramp_launches": ramp_n,
             "device_ramp_ms": round(ramp_ms, 1),
             "higher_is_better": True,

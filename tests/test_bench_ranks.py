@@ -83,6 +83,23 @@ def test_bench_gpus1_runs_one_rank(hostcheck):
     assert np.array_equal(np.array(line["config"]["rank_totals"], np.int64), want)
 
 
+def test_bench_plain_run_and_dump_outputs(hostcheck, tmp_path):
+    """A plain run (no --full, nothing switched off by hand) measures no CPU
+    baseline and runs no checker leg, and --dump-outputs writes what the last
+    timed launch left: here its per-256-env totals rows (the host engine has
+    no per-ply buffers)."""
+    p = _run(["--gpus", "1", "--steps", "8", "--warmup", "2", "--plies-per-launch", "4", "--envs", "512",
+              "--dump-outputs", str(tmp_path)])
+    line = _line(p)
+    assert line["full"] is False and line["cpu_baseline"] is None and line["parity_check"] is None
+    assert line["steps"] == 8 and line["ms_per_step"] > 0
+    assert line["dumped_outputs"] == ["totals_rows"]
+    rows = np.load(tmp_path / "totals_rows.npy")
+    assert rows.dtype == np.float64 and rows.shape == (2, 3)
+    want = _oracle_rank_totals(256, 2, 3 * 2 * 4 + 2 + 8, seed=0)  # rows = the two 256-env workgroups
+    assert np.array_equal(rows, want.astype(np.float64))
+
+
 @pytest.mark.parametrize("world", [4])
 def test_bench_gpus4_rank_totals(hostcheck, world):
     p = _run(["--gpus", str(world), "--steps", "10", "--warmup", "0", "--plies-per-launch", "10",
@@ -96,12 +113,12 @@ def test_bench_gpus4_rank_totals(hostcheck, world):
 def test_bench_gpus8_scale_line(hostcheck):
     """the N = 8 line the driver's SCALE run prints --
     8 ranks, configs[4] named at 8 x 65,536 global envs, a CPU baseline
-    measured by the launching process before the ranks start, and every
+    (--full) measured by the launching process before the ranks start, and every
     rank's totals equal to the oracle on the same global env ids."""
     steps, ppl = 4, 4
     quiet = [a for a in QUIET if a != "--no-cpu-baseline"]
     p = _run(["--gpus", "8", "--steps", str(steps), "--warmup", "0", "--plies-per-launch", str(ppl),
-              "--envs", "65536", "--cpu-seconds", "0.3", "--cpu-cores", "2", *quiet], timeout=600)
+              "--envs", "65536", "--full", "--cpu-seconds", "0.3", "--cpu-cores", "2", *quiet], timeout=600)
     line = _line(p)
     assert line["n_gpus"] == 8
     cfg = line["config"]

@@ -3,6 +3,7 @@ the network is the reference's (train_deepq_pytorch.py:184-222), the move-2
 column-gather equals the reference's one-hot concat, the mask helpers, and the
 prioritized replay rules (:279-342).  The env-facing parts run on the GPU
 (tests/test_gpu_dqn.py)."""
+import glob
 import os
 
 import numpy as np
@@ -10,6 +11,8 @@ import pytest
 import torch
 
 from gym_narde.dqn import DecomposedDQN, DeviceReplay, expand_mask, masked_argmax
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def reference_move2(model, x, m1):
@@ -43,13 +46,27 @@ def test_parameter_names_match_reference():
         "move2_head.weight": (576, 832), "move2_head.bias": (576,)}
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/saved_models/narde_model_final.pt"),
-                    reason="reference checkpoint not present (it never travels to the GPU box)")
+def reference_checkpoint():
+    """The reference's trained checkpoint (saved_models/narde_model_final.pt)
+    as stored under tests/golden/ by tools/capture_checkpoint.py: every
+    tensor bit for bit, the large one in row pieces `<key>@<first row>`."""
+    pieces = {}
+    for path in sorted(glob.glob(os.path.join(GOLDEN, "checkpoint_*.npz"))):
+        pieces.update(np.load(path, allow_pickle=False))
+    sd = {}
+    for name in sorted(pieces, key=lambda n: (n.split("@")[0], int(n.split("@")[1]) if "@" in n else 0)):
+        sd.setdefault(name.split("@")[0], []).append(torch.from_numpy(pieces[name]))
+    return {k: torch.cat(v) for k, v in sd.items()}
+
+
 def test_reference_checkpoint_loads():
-    sd = torch.load("/root/reference/saved_models/narde_model_final.pt", weights_only=True,
-                    map_location="cpu")
+    sd = reference_checkpoint()
     m = DecomposedDQN(24)
     m.load_state_dict(sd, strict=True)
+    assert all(torch.equal(v, sd[k]) and v.dtype == torch.float32 for k, v in m.state_dict().items())
+    # trained weights, not an initialisation: the reference's nn.Linear
+    # default draws are bounded by 1/sqrt(fan_in)
+    assert float(sd["feature_network.0.weight"].abs().max()) > 1.0
 
 
 def test_expand_mask_and_masked_argmax():

@@ -8,7 +8,7 @@ N=${1:-2}
 mkdir -p gpurun_out/rehearse
 export NARDE_REHEARSAL=1
 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --steps 2000 --warmup 200 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --full --steps 2000 --warmup 200 \
   --dqn-steps 5 --api-steps 50 --other-launches 5 > gpurun_out/rehearse/bench_n$N.json \
   2> gpurun_out/rehearse/bench_n$N.err
 rc=$?

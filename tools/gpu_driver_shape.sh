@@ -30,10 +30,10 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
   timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit $?
 fi
 echo "[gpu] $(date +%T) bench --steps $S --warmup $W"
-timeout -k 10 300 python bench.py --gpus 1 --steps $S --warmup $W > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" \
+timeout -k 10 300 python bench.py --gpus 1 --steps $S --warmup $W --full > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" \
   && echo "[gpu] $(date +%T) rocprof kernel trace (same command)" \
   && (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/rocprof_driver" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps $S --warmup $W --no-cpu-baseline \
+        -d "$OUT/rocprof_driver" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps $S --warmup $W --full --no-cpu-baseline \
         > "$OUT/rocprof_driver.log" 2>&1) \
   && echo "[gpu] $(date +%T) pmc FETCH_SIZE at $S plies" \
   && (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv \

@@ -13,13 +13,13 @@ T="python -u -m pytest -x -v --timeout 200 --timeout-method thread"
 case "$PHASE" in
 parity)  # the full-batch parity tests and the self-checking bench line
   timeout -k 10 400 $T tests/test_gpu_parity.py tests/test_gpu_full4.py -m gpu > "$OUT/pytest.log" 2>&1 \
-    && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" \
-    && timeout -k 10 300 python bench.py --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+    && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_driver.json" 2> "$OUT/bench_driver.err" \
+    && timeout -k 10 300 python bench.py --full --no-cpu-baseline > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
   rc=$?; tail -3 "$OUT/pytest.log"; exit $rc ;;
 drv)  # the driver's command, with and without the checker leg, alternating
   for k in 1 2 3; do
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/drv_chk_$k.json" 2> "$OUT/drv_chk_$k.err" \
-      && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-parity-check --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/drv_chk_$k.json" 2> "$OUT/drv_chk_$k.err" \
+      && timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-parity-check --no-cpu-baseline \
            > "$OUT/drv_nochk_$k.json" 2> "$OUT/drv_nochk_$k.err" || exit 1
   done ;;
 clock)  # per-wave stamps of the driver's timed REF2 launch (tools/diag/build_clock.py, built beforehand)
@@ -43,8 +43,8 @@ ab)  # sustained FULL4 20 / 1,000-ply rollouts of tools/diag/build/libnarde_<tag
 plan)  # the driver's command with the pre-bound timed launch and without it, alternating
   timeout -k 10 300 $T tests/test_gpu_parity.py -m gpu -k "plan or totals_rows" > "$OUT/pytest_plan.log" 2>&1 || exit 1
   for k in 1 2 3 4; do
-    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/plan1_$k.json" 2> "$OUT/plan1_$k.err" \
-      && NARDE_ROLLOUT_PLAN=0 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
+    timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline > "$OUT/plan1_$k.json" 2> "$OUT/plan1_$k.err" \
+      && NARDE_ROLLOUT_PLAN=0 timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline \
            > "$OUT/plan0_$k.json" 2> "$OUT/plan0_$k.err" || exit 1
   done ;;
 single)  # one 20-ply launch after an idle synchronize (the driver's shape), per library in $TAGS, 2 rounds
@@ -74,9 +74,9 @@ sus)  # sustained REF2 and FULL4 rollouts at $PLIES plies per launch per library
   rc=$?; cat "$OUT/sus.log"; exit $rc ;;
 libab)  # bench.py's default (1,000-ply) and driver lines per library in $TAGS, alternating, 2 rounds
   for rep in 1 2; do for tag in $TAGS; do
-    NARDE_LIB=$PWD/tools/diag/build/libnarde_$tag.so timeout -k 10 300 python bench.py --no-cpu-baseline \
+    NARDE_LIB=$PWD/tools/diag/build/libnarde_$tag.so timeout -k 10 300 python bench.py --full --no-cpu-baseline \
       > "$OUT/def_${tag}_$rep.json" 2> "$OUT/def_${tag}_$rep.err" \
-    && NARDE_LIB=$PWD/tools/diag/build/libnarde_$tag.so timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 \
+    && NARDE_LIB=$PWD/tools/diag/build/libnarde_$tag.so timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full \
       --no-cpu-baseline > "$OUT/drv_${tag}_$rep.json" 2> "$OUT/drv_${tag}_$rep.err" || exit 1
   done; done ;;
 libdqn)  # the DQN tests on the product, then the driver timed with libnarde_$BASE.so and the product, alternating, then traced

@@ -45,21 +45,21 @@ if [ "$PHASE" = run ]; then
     && echo "[gpu_round] $(date +%T) smoke" \
     && timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
     && echo "[gpu_round] $(date +%T) bench (driver shape x3)" \
-    && for k in 1 2 3; do timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 \
+    && for k in 1 2 3; do timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full \
          > "$OUT/bench_driver_$k.json" 2> "$OUT/bench_driver_$k.err" || exit 1; done \
     && echo "[gpu_round] $(date +%T) bench (default)" \
-    && timeout -k 10 300 python bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err" \
+    && timeout -k 10 300 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err" \
     && echo "[gpu_round] $(date +%T) bench --rules full4 (driver shape, default)" \
-    && timeout -k 10 300 python bench.py --rules full4 --steps 20 --warmup 5 --no-cpu-baseline \
+    && timeout -k 10 300 python bench.py --rules full4 --steps 20 --warmup 5 --full --no-cpu-baseline \
          > "$OUT/bench_full4_driver.json" 2> "$OUT/bench_full4_driver.err" \
-    && timeout -k 10 300 python bench.py --rules full4 --no-cpu-baseline > "$OUT/bench_full4.json" 2> "$OUT/bench_full4.err" \
+    && timeout -k 10 300 python bench.py --rules full4 --full --no-cpu-baseline > "$OUT/bench_full4.json" 2> "$OUT/bench_full4.err" \
     && echo "[gpu_round] $(date +%T) rocprof kernel trace (driver shape)" \
     && (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$OUT/rocprof_driver" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline \
+          -d "$OUT/rocprof_driver" -o bench -- python3 "$ROOT/bench.py" --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline \
           > "$OUT/rocprof_driver.log" 2>&1) \
     && echo "[gpu_round] $(date +%T) rocprof kernel trace (default bench)" \
     && (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \
-          -d "$OUT/rocprof_bench" -o bench -- python3 "$ROOT/bench.py" --no-cpu-baseline \
+          -d "$OUT/rocprof_bench" -o bench -- python3 "$ROOT/bench.py" --full --no-cpu-baseline \
           > "$OUT/rocprof_bench.log" 2>&1) \
     && echo "[gpu_round] $(date +%T) done"
   rc=$?
