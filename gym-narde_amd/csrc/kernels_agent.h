@@ -56,28 +56,6 @@ struct TransArgs {
   int64_t capacity;
 };
 
-// value of column col of the 198-float observation of a record (k_observe's
-// layout), branch-free: the 64 lanes of a wave hold 64 consecutive columns,
-// so per-column branches would run every case on every wave
-__device__ __forceinline__ float tes_value(uint4 a, uint4 b, int col) {
-  const bool black = (b.z >> 10) & 1u;
-  const float player = (col == 196) != black ? 1.0f : 0.0f;
-  const int side = col >= 98 ? 1 : 0;
-  const int cc = col - 98 * side;
-  const float offv = (float)(side ? ((b.z >> 4) & 15u) : (b.z & 15u)) / 15.0f;
-  const int pt = cc < 96 ? (cc >> 2) : 0;
-  const uint32_t w0 = side ? a.z : a.x, w1 = side ? a.w : a.y, w2 = side ? b.y : b.x;
-  const int k = pt >> 3;
-  const uint32_t word = k == 0 ? w0 : (k == 1 ? w1 : w2);
-  const uint32_t v = (word >> (4 * (pt & 7))) & 15u;
-  const int j = cc & 3;
-  const float thr = v >= (uint32_t)(j + 1) ? 1.0f : 0.0f;  // j = 0, 1, 2: v >= 1, 2, 3
-  const float over = v >= 3u ? (float)(v - 3u) / 2.0f : 0.0f;
-  const float board = j == 3 ? over : thr;
-  const float pv = cc == 96 ? 0.0f : (cc == 97 ? offv : board);
-  return col >= 196 ? player : pv;
-}
-
 // The 198-float observation, a wave per 16 envs: lane l computes a quarter
 // of env (l & 15)'s row -- quarter q = l >> 4: white points 0-11 (columns
 // 0-47), white points 12-23 + bar + off (48-97), black points 0-11
@@ -102,15 +80,9 @@ __device__ __forceinline__ void tes_point4(uint32_t v, float* f) {
   f[3] = v >= 3u ? (float)(v - 3u) / 2.0f : 0.0f;
 }
 
-// the wave's 16 rows (envs e0 .. e0 + 15, those below n) into wave_rows
-// (LDS, 16 x 198 floats); the caller hands them over with wave_lds_handoff
-__device__ __forceinline__ void tes_stage_rows(const Planes& pl, int n, int e0, float* wave_rows) {
-  const int lane = threadIdx.x & 63;
-  const int le = lane & 15, q = lane >> 4;
-  const int i = e0 + le;
-  float* row = wave_rows + le * 198;
-  if (i < n) {
-    const uint4 a = pl.p0[i], b = pl.p1[i];
+// quarter q of record (a, b)'s row into row (LDS, 198 floats, 8-B aligned)
+__device__ __forceinline__ void tes_stage_quarter(const uint4 a, const uint4 b, int q, float* row) {
+  {
     const int side = q >> 1, upper = q & 1;
     const uint32_t w0 = side ? a.z : a.x, w1 = side ? a.w : a.y, w2 = side ? b.y : b.x;
     // points 12q' .. 12q' + 11 of the side: 8 nibbles in X, 4 in Y
@@ -135,6 +107,15 @@ __device__ __forceinline__ void tes_stage_rows(const Planes& pl, int n, int e0, 
     for (int k = 0; k < 26; ++k)
       if (2 * k < nf) *reinterpret_cast<float2*>(row + c0 + 2 * k) = make_float2(f[2 * k], f[2 * k + 1]);
   }
+}
+
+// the wave's 16 rows (envs e0 .. e0 + 15, those below n) into wave_rows
+// (LDS, 16 x 198 floats); the caller hands them over with wave_lds_handoff
+__device__ __forceinline__ void tes_stage_rows(const Planes& pl, int n, int e0, float* wave_rows) {
+  const int lane = threadIdx.x & 63;
+  const int le = lane & 15, q = lane >> 4;
+  const int i = e0 + le;
+  if (i < n) tes_stage_quarter(pl.p0[i], pl.p1[i], q, wave_rows + le * 198);
 }
 
 __global__ void __launch_bounds__(kBlock) k_tesauro198_rows(Planes pl, int n, float* __restrict__ tes) {

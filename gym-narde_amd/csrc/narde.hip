@@ -17,6 +17,8 @@
 //                       and k_rollout_pp_full (FULL4)
 //   kernels_agent.h     observations, move masks, the policy kernel, the DQN
 //                       transition
+//   kernels_afterstates.h  afterstate expansion (count, scan, fill) and the
+//                       value-greedy pick
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip).
 #include <hip/hip_runtime.h>
@@ -59,6 +61,7 @@ int fail(int code, const char* fmt, ...) {
 #include "kernels_full4.h"
 #include "kernels_rollout.h"
 #include "kernels_agent.h"
+#include "kernels_afterstates.h"
 
 namespace {
 
@@ -606,6 +609,45 @@ int narde_explore_plays(narde_env* e, const uint8_t* dice, const float* epsilon,
                                                                   (uint32_t)seed, (uint32_t)(seed >> 32), out,
                                                                   ld_out);
   return check_launch("k_explore_plays");
+}
+
+int narde_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
+                      int16_t* codes, float* feat, int32_t* obs, int8_t* reward, void* stream) {
+  if (!e || !offsets) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (e->n * kAftMaxPlays >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", kAftMaxPlays);
+  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
+      (reinterpret_cast<uintptr_t>(codes) % 4))
+    return fail(NARDE_EINVAL, "feat and obs must be 16-B aligned, codes 4-B aligned");
+  DeviceGuard dg(e->device);
+  AftArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, feat, obs, reward};
+  const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
+  k_aft_count<<<(unsigned)((e->n + cw - 1) / cw), kAftCountBlock, 0, (hipStream_t)stream>>>(a);
+  if (const int rc = check_launch("k_aft_count")) return rc;
+  k_aft_scan<<<1, kAftScanBlock, 0, (hipStream_t)stream>>>(offsets, (int)e->n);
+  if (const int rc = check_launch("k_aft_scan")) return rc;
+  if (cap == 0 || !(row_env || codes || feat || obs || reward)) return NARDE_OK;
+  k_aft_fill<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, (hipStream_t)stream>>>(a);
+  return check_launch("k_aft_fill");
+}
+
+int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* codes, int64_t cap,
+                          const float* value, int64_t ld_value, int perspective, const float* epsilon,
+                          uint64_t seed, const int64_t* tag, int16_t* actions, int32_t* row, void* stream) {
+  if (!e || !offsets || !codes || !value || !actions) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (perspective != 0 && perspective != 1)
+    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if (epsilon && !tag) return fail(NARDE_EINVAL, "exploration needs a tag");
+  if ((reinterpret_cast<uintptr_t>(codes) % 4) || (reinterpret_cast<uintptr_t>(actions) % 4))
+    return fail(NARDE_EINVAL, "codes and actions must be 4-B aligned");
+  DeviceGuard dg(e->device);
+  k_aft_pick<<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(e->pl, (int)e->n, offsets, codes, cap, value, ld_value,
+                                                             perspective, epsilon, tag, (uint32_t)seed,
+                                                             (uint32_t)(seed >> 32), actions, row);
+  return check_launch("k_aft_pick");
 }
 
 int narde_policy_masked_argmax576(int device, const float* q, int64_t ldq, const uint64_t* mask, int64_t n,

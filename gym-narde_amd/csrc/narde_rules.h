@@ -441,6 +441,15 @@ NARDE_FN void apply_move(Side& s, int f, int t) {
 
 NARDE_FN uint32_t mulhi_u32(uint32_t r, uint32_t n) { return (uint32_t)(((uint64_t)r * n) >> 32); }
 
+// the end of NardeEnv.step once its moves are applied: _check_game_ended
+// (narde_env.py:134-141: only the mover is checked), then the mover change
+// (:99-100) unless the game ended
+NARDE_FN void step_end(Side& s, bool flip_always, int& term, int& reward) {
+  term = s.off_own == 15u;
+  reward = term ? (s.off_opp > 0u ? 1 : 2) : 0;
+  if (flip_always || !term) side_flip(s);
+}
+
 struct StepOut {
   Legal l1;
   uint32_t L2;
@@ -521,10 +530,7 @@ NARDE_FN void env_step(Side& s, int d0, int d1, int code1, int code2, bool polic
   }
   o.code1 = code1;
   o.code2 = code2;
-  // _check_game_ended (narde_env.py:134-141): only the mover is checked
-  o.term = s.off_own == 15u;
-  o.reward = o.term ? (s.off_opp > 0u ? 1 : 2) : 0;
-  if (flip_always || !o.term) side_flip(s);
+  step_end(s, flip_always, o.term, o.reward);
 }
 
 // ============================================================ play sets
@@ -552,6 +558,31 @@ constexpr int kPlayAct = 0;
 constexpr int kPlayStep = 1;
 constexpr uint32_t kPlayValid = 1u << 27;
 
+// the kPlayStep word of list-#1 entry (p, die) (n1 = the list's length) and
+// the plays it counts for: a one-entry list is played alone
+// (narde_env.py:41-43), a duplicate entry adds none, an empty second list
+// leaves move 1 alone
+NARDE_FN uint32_t play_step_word(const Side& s, int d0, int d1, int n1, int p, int die) {
+  if (n1 == 1) return kPlayValid;
+  const bool off = p < die;
+  Side c = s;
+  apply_move(c, p, off ? OFF : p - die);
+  const int dist = off ? p + 1 : die;
+  const int rem = (d0 == dist) ? d1 : ((d1 == dist) ? d0 : d1);
+  const uint32_t L2 = die_filter(c.O, c.S1o, block_info(c.O, c.P), die_candidates(c.O, c.P, rem), rem);
+  return L2 | ((uint32_t)rem << 24) | kPlayValid;
+}
+NARDE_FN int play_step_count(int n1, uint32_t word, bool dup) {
+  if (n1 == 1) return 1;
+  const int c2 = __builtin_popcount(word & 0xFFFFFFu);
+  return dup ? 0 : (c2 > 0 ? c2 : 1);
+}
+// is entry p of the lower die's list (k = 1) the same move as one of the
+// higher die's (doubles, or a bear-off both dice reach)?
+NARDE_FN bool play_entry_dup(const Legal& l, int k, int p) {
+  return k == 1 && ((l.L[0] >> p) & 1u) && (l.d[0] == l.d[1] || p < l.d[1]);
+}
+
 // visit(k, p, die, word, dup) for every entry of list #1 in list order;
 // returns the play count.  l: legal2(s, d0, d1) (dice in roll order).
 template <class F>
@@ -569,7 +600,7 @@ NARDE_FN int play_walk(const Side& s, int d0, int d1, int kind, const Legal& l, 
       const int p = __builtin_ctz(m);
       m &= m - 1u;
       const bool off = p < die;
-      const bool dup = k == 1 && ((l.L[0] >> p) & 1u) && (l.d[0] == l.d[1] || off);
+      const bool dup = play_entry_dup(l, k, p);
       uint32_t word;
       if (kind == kPlayAct) {
         const bool first = off ? d0 >= p + 1 : d0 == die;  // act() matched roll[0]
@@ -577,20 +608,9 @@ NARDE_FN int play_walk(const Side& s, int d0, int d1, int kind, const Legal& l, 
         word = (first ? M1 : M0) | ((uint32_t)rem << 24) | kPlayValid;
         const int c2 = __builtin_popcount(word & 0xFFFFFFu);
         count += c2 > 0 ? c2 : 1;
-      } else if (n1 == 1) {
-        word = kPlayValid;  // narde_env.py:41-43: played alone
-        count = 1;
       } else {
-        Side c = s;
-        apply_move(c, p, off ? OFF : p - die);
-        const int dist = off ? p + 1 : die;
-        const int rem = (d0 == dist) ? d1 : ((d1 == dist) ? d0 : d1);
-        const uint32_t L2 = die_filter(c.O, c.S1o, block_info(c.O, c.P), die_candidates(c.O, c.P, rem), rem);
-        word = L2 | ((uint32_t)rem << 24) | kPlayValid;
-        if (!dup) {
-          const int c2 = __builtin_popcount(L2);
-          count += c2 > 0 ? c2 : 1;
-        }
+        word = play_step_word(s, d0, d1, n1, p, die);
+        count += play_step_count(n1, word, dup);
       }
       visit(k, p, die, word, dup);
     }
@@ -645,6 +665,99 @@ NARDE_FN void act_masks(const Side& s, int d0, int d1, const Legal& l, int move1
     const int c = encode_move(q, q < rem ? OFF : q - rem);
     m[c >> 6] |= 1ull << (c & 63);
   }
+}
+
+// ============================================================ afterstates
+// The successor positions of a roll (VecNardeEnv.afterstates, DESIGN.md
+// section 13): the kPlayStep plays in play_walk's enumeration order -- list
+// #1's entries in list order, duplicates skipped, the second-move sources
+// ascending; an entry with an empty second list, or a one-entry list #1, is
+// a one-move play -- less the plays action codes cannot express, each
+// carried out as NardeEnv.step does (narde_env.py:27-103), the first of the
+// plays that leave the same board and off counts kept.
+struct Play {
+  int f1, t1;
+  int f2, t2;  // f2 < 0: a one-move play
+};
+
+// play r (0 <= r < play_step_count) of list-#1 entry (p, die) with kPlayStep
+// word `word`
+NARDE_FN Play play_of_entry(int p, int die, uint32_t word, int r) {
+  Play y;
+  y.f1 = p;
+  y.t1 = p < die ? OFF : p - die;
+  const uint32_t m2 = word & 0xFFFFFFu;
+  const int rem = (int)((word >> 24) & 7u);
+  const int q = select_bit(m2, r);
+  y.f2 = m2 ? q : -1;
+  y.t2 = q < rem ? OFF : q - rem;
+  return y;
+}
+
+// can a code request the move?  decode(encode(f, t)) differs from (f, t) for
+// a normal move landing on point 0 from 1..5 (the reference's 'off' quirk)
+NARDE_FN bool move_expressible(int f, int t) {
+  int g, u;
+  decode_action(encode_move(f, t), g, u);
+  return g == f && u == t;
+}
+
+// one_entry: list #1 has one entry, which the step plays whatever the action
+NARDE_FN bool play_expressible(const Play& y, bool one_entry) {
+  return one_entry || (move_expressible(y.f1, y.t1) && (y.f2 < 0 || move_expressible(y.f2, y.t2)));
+}
+
+NARDE_FN void play_codes(const Play& y, int& c1, int& c2) {
+  c1 = encode_move(y.f1, y.t1);
+  c2 = y.f2 < 0 ? 0 : encode_move(y.f2, y.t2);
+}
+
+// Board + off identity of the play's afterstate as a 20-bit key.  A play
+// takes one checker off each source and puts one on each target ('off' =
+// point 24); a point that is one move's target and the other's source
+// cancels (t1 == f2: a checker moved twice; t2 == f1: move 2 refills move
+// 1's source; never both, moves go down).  What is left is a multiset of <= 2
+// sources and one of as many targets with no point in both, so two plays
+// leave the same position iff both multisets agree: each sorted, 5 bits a
+// point, 31 for a missing second one.
+NARDE_FN uint32_t play_key(const Play& y) {
+  uint32_t sa = (uint32_t)y.f1, sb = 31u, ta = (uint32_t)y.t1, tb = 31u;
+  if (y.f2 >= 0) {
+    if (y.t1 == y.f2) {
+      ta = (uint32_t)y.t2;
+    } else if (y.t2 == y.f1) {
+      sa = (uint32_t)y.f2;
+    } else {
+      sb = (uint32_t)y.f2;
+      tb = (uint32_t)y.t2;
+    }
+  }
+  const uint32_t s0 = sa < sb ? sa : sb, s1 = sa < sb ? sb : sa;
+  const uint32_t t0 = ta < tb ? ta : tb, t1 = ta < tb ? tb : ta;
+  return s0 | (s1 << 5) | (t0 << 10) | (t1 << 15);
+}
+
+// the play carried out as env_step does for its codes: the moves, then the
+// step's end (the mover is not flipped after a terminal step)
+NARDE_FN void play_afterstate(Side& s, const Play& y, int& term, int& reward) {
+  apply_move(s, y.f1, y.t1);
+  if (y.f2 >= 0) apply_move(s, y.f2, y.t2);
+  step_end(s, false, term, reward);
+}
+
+// play j (0 <= j < play_walk's kPlayStep count) in enumeration order;
+// false past the end
+NARDE_FN bool play_step_at(const Side& s, int d0, int d1, const Legal& l, int j, Play& y) {
+  int left = j;
+  bool found = false;
+  play_walk(s, d0, d1, kPlayStep, l, [&](int, int p, int die, uint32_t word, bool dup) {
+    if (found) return;
+    const int w = play_step_count(l.count, word, dup);
+    if (left >= w) { left -= w; return; }
+    found = true;
+    y = play_of_entry(p, die, word, left);
+  });
+  return found;
 }
 
 // ============================================================ FULL4 turns
@@ -1837,6 +1950,28 @@ NARDE_FN void turn_c0_pair_bound_w(const Side& s, int dh, int dl, uint32_t hs, u
 
 // obs = get_perspective_board(current_player) (narde.py:31-34): int32[24]
 NARDE_FN int obs_point(const Side& s, int p) { return (int)nib_get(s.own, p) - (int)nib_get(s.opp, p); }
+
+// value of column col of the 198-float observation of a record (README.md:42-102;
+// k_tesauro198_rows' layout), branch-free: the 64 lanes of a wave hold 64 consecutive columns,
+// so per-column branches would run every case on every wave
+NARDE_FN float tes_value(uint4 a, uint4 b, int col) {
+  const bool black = (b.z >> 10) & 1u;
+  const float player = (col == 196) != black ? 1.0f : 0.0f;
+  const int side = col >= 98 ? 1 : 0;
+  const int cc = col - 98 * side;
+  const float offv = (float)(side ? ((b.z >> 4) & 15u) : (b.z & 15u)) / 15.0f;
+  const int pt = cc < 96 ? (cc >> 2) : 0;
+  const uint32_t w0 = side ? a.z : a.x, w1 = side ? a.w : a.y, w2 = side ? b.y : b.x;
+  const int k = pt >> 3;
+  const uint32_t word = k == 0 ? w0 : (k == 1 ? w1 : w2);
+  const uint32_t v = (word >> (4 * (pt & 7))) & 15u;
+  const int j = cc & 3;
+  const float thr = v >= (uint32_t)(j + 1) ? 1.0f : 0.0f;  // j = 0, 1, 2: v >= 1, 2, 3
+  const float over = v >= 3u ? (float)(v - 3u) / 2.0f : 0.0f;
+  const float board = j == 3 ? over : thr;
+  const float pv = cc == 96 ? 0.0f : (cc == 97 ? offv : board);
+  return col >= 196 ? player : pv;
+}
 
 // ------------------------------------------------------------- Philox4x32-10
 NARDE_FN void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

@@ -1,0 +1,57 @@
+"""Value-greedy play on VecNardeEnv: the TD-Gammon way to choose a move.
+
+A TD-Gammon agent (the reference's README: the 198-float Tesauro encoding,
+README.md:42-102, reward "+1 if WHITE wins") does not score action codes: it
+scores the positions a roll can lead to -- the afterstates -- with a value
+network and plays the best one.  ValuePlayer does that for B envs at once,
+everything on the device: VecNardeEnv.afterstates() expands the roll,
+`net` scores the rows, VecNardeEnv.pick_afterstate() chooses, step() plays.
+"""
+
+
+class ValuePlayer:
+    """net: a callable (R,198) float32 -> (R,) or (R,1) values (a
+    torch.nn.Module on the env's device).  perspective "white": the values
+    are white's (the README's reward) -- white plays the largest, black the
+    smallest; "mover": they are the side's that has just moved -- always the
+    largest."""
+
+    def __init__(self, env, net, perspective="white"):
+        from .vector import PERSPECTIVES
+
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        if env.full:
+            raise ValueError('ValuePlayer is rules="ref2" only')
+        self.env, self.net, self.perspective = env, net, perspective
+
+    def values(self, aft):
+        """net(feat), with the rows that end the game set to their known
+        outcome: the step's reward (1, or 2 when the loser has borne off
+        nothing) for the side that made the move -- negated in white's
+        perspective when that side is black."""
+        t = self.env.torch
+        if aft.cap == 0:
+            return t.empty(0, dtype=t.float32, device=self.env.device)
+        with t.no_grad():
+            v = self.net(aft.feat).reshape(-1).to(t.float32)
+        outcome = aft.reward.to(t.float32)
+        if self.perspective == "white":
+            # after a terminal step the mover is not flipped: the row's player
+            # one-hot (columns 196 white, 197 black) names the winner
+            outcome = t.where(aft.feat[:, 197] > 0.5, -outcome, outcome)
+        return t.where(aft.reward != 0, outcome, v)
+
+    def step(self, epsilon=None, tag=None, seed=0):
+        """One ply for every env: the next step's dice, their afterstates, the
+        values, the pick, the step.  Returns (obs, reward, terminated,
+        truncated, info, aft, values, actions); an env with no expressible
+        play steps with (0, 0), which moves nothing."""
+        env = self.env
+        dice = env.dice()
+        aft = env.afterstates(dice)
+        values = self.values(aft)
+        actions, row = env.pick_afterstate(aft, values, self.perspective, epsilon, tag, seed)
+        obs, reward, terminated, truncated, info = env.step(actions)
+        info = dict(info, dice=dice, row=row)
+        return obs, reward, terminated, truncated, info, aft, values, actions

@@ -20,6 +20,7 @@ dice used, the higher die when only one can be used.  Its actions are plays,
 set with the max dice usable in bits 56-58, info["played"] the sub-moves
 played (bytes 2k/2k+1 = from/die, 0xFF unused).
 """
+import collections
 import ctypes
 import os
 import weakref
@@ -109,6 +110,14 @@ def decode_play_set(legal, words, kind="act"):
         else:
             out.update((m1, m2_) for m2_ in seconds)
     return out
+
+
+PERSPECTIVES = {"mover": 0, "white": 1}
+
+# VecNardeEnv.afterstates' result: CSR rows (env e's rows are offsets[e] ..
+# offsets[e + 1] - 1); cap = the rows the arrays hold -- offsets[B] > cap
+# means the call overflowed and the rows from cap on were not written
+Afterstates = collections.namedtuple("Afterstates", "offsets row_env codes feat obs reward cap")
 
 
 class VecNardeEnv:
@@ -328,6 +337,97 @@ class VecNardeEnv:
                          _lib.ptr(tag), _lib.ptr(actions), actions.stride(0), self._s())
         self._keep = (d,)
         return actions
+
+    def afterstates(self, dice=None, cap=None, feat=True, obs=False, out=None):
+        """The successor positions of each env's roll (narde_afterstates; what
+        a TD-Gammon value network scores, README.md:42-102), for dice (B,2) in
+        roll order or the next step's device dice: per env the plays
+        NardeEnv.step carries out (narde_env.py:27-103) in list order, less
+        those action codes cannot express, the first of those that leave the
+        same board and off counts kept.  Returns Afterstates(offsets (B+1,)
+        int32, row_env (R,) int32, codes (R,2) int16 -- feed them to step()
+        --, feat (R,198) float32 = tesauro198() after that step, obs (R,24)
+        int32 or None, reward (R,) int8 -- 0, or 1 / 2 at a terminal
+        afterstate --, cap = R).
+        cap None: a count pass, then offsets[B] is read on the host -- the
+        call's ONE synchronise -- and the arrays are allocated exactly.  cap
+        given (or out: an Afterstates of preallocated arrays, cap rows of
+        them used): one stream-ordered call with no synchronise, safe to
+        capture in a graph; rows from cap on are not written, and offsets
+        still holds the true counts."""
+        if self.full:
+            raise ValueError('afterstates() is rules="ref2" only')
+        B, t = self.num_envs, self.torch
+        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        if out is not None:
+            offsets = out.offsets
+            cap = out.cap if cap is None else int(cap)
+            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
+                                       ("codes", out.codes, (2,), t.int16), ("feat", out.feat, (198,), t.float32),
+                                       ("obs", out.obs, (24,), t.int32), ("reward", out.reward, (), t.int8)):
+                if a is None:
+                    continue
+                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
+                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
+                if not ok:
+                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
+        else:
+            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
+            if cap is None:
+                self.handle.call("narde_afterstates", _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None,
+                                 None, self._s())
+                cap = int(offsets[B].item())  # the one synchronise
+            cap = int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
+            out = Afterstates(offsets, mk(True, (), t.int32), mk(True, (2,), t.int16), mk(feat, (198,), t.float32),
+                              mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        rows = (out.row_env, out.codes, out.feat, out.obs, out.reward)
+        self.handle.call("narde_afterstates", _lib.ptr(d), cap, _lib.ptr(offsets),
+                         *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
+        self._keep = (d,)
+        return out._replace(cap=cap)
+
+    def pick_afterstate(self, aft, values, perspective="white", epsilon=None, tag=None, seed=0):
+        """Value-greedy play (narde_afterstate_pick): per env the row of `aft`
+        with the best of values (one float32 per row of aft.feat: (R,) or
+        (R,1), any row stride) -- perspective "mover": the largest;
+        "white" (the README's reward, +1 if WHITE wins): the largest when
+        white moves, the smallest when black does; the lowest row on ties.
+        epsilon (f32) / tag (int64) device scalars (or numbers): the env's
+        explore draw ({tag, env, 0, 5}, seed) below epsilon takes a uniform
+        row instead.  Call it before the step (it reads who moves).
+        Returns (actions (B,2) int16 for step(), row (B,) int32; -1 and
+        (0, 0) for an env with no row)."""
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        B, t = self.num_envs, self.torch
+        v = values
+        if v.dim() == 2 and v.shape[1] == 1:
+            v = v[:, 0]
+        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
+                or (v.shape[0] > 1 and v.stride(0) < 1)):
+            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
+        if (epsilon is None) != (tag is None):
+            raise ValueError("epsilon and tag go together")
+        if epsilon is not None:
+            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
+            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+        actions = t.empty((B, 2), dtype=t.int16, device=self.device)
+        row = t.empty(B, dtype=t.int32, device=self.device)
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            actions.zero_()
+            row.fill_(-1)
+            return actions, row
+        self.handle.call("narde_afterstate_pick", _lib.ptr(aft.offsets), _lib.ptr(aft.codes), aft.cap, _lib.ptr(v),
+                         max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
+                         _lib.ptr(tag), _lib.ptr(actions), _lib.ptr(row), self._s())
+        self._keep = (v, epsilon, tag)
+        return actions, row
 
     def legal_full(self, dice=None):
         """FULL4: (B,) int64 legal words (first sub-move set | max dice << 56)

@@ -293,6 +293,52 @@ int narde_act_masks(narde_env *env, const uint8_t *dice, const int64_t *move1, i
 int narde_explore_plays(narde_env *env, const uint8_t *dice, const float *epsilon, uint64_t seed,
                         const int64_t *tag, int64_t *out, int64_t ld_out, void *stream);
 
+/* Afterstates: the successor positions of each env's two-dice roll (REF2),
+ * what a TD-Gammon value network scores (README.md:42-102 the 198-float
+ * encoding, README.md:156-165 get_valid_actions).  dice u8[B][2] in roll
+ * order (NULL = the next step's device dice).  Per env, the plays
+ * NardeEnv.step carries out (narde_env.py:27-103; narde_play_set kind 1) in
+ * list order -- list #1's entries in list order, duplicate entries skipped,
+ * the second-move sources ascending; an entry with no second move, or a
+ * one-entry list #1, is a one-move play -- keeping only plays whose moves
+ * action codes express (decode(encode(f, t)) == (f, t): not a normal move
+ * landing on point 0 from 1..5; a one-entry list #1 is played whatever the
+ * action and always kept), each carried out as narde_step(actions = (c1,
+ * c2), dice, autoreset = 0) does, and of the plays that leave the same board
+ * and off counts only the first.  Rows are CSR: env e's rows are
+ * offsets[e] .. offsets[e + 1] - 1 (offsets i32[B + 1], offsets[0] = 0), in
+ * that order, the same on every call (no atomics).  A die outside 1..6 or no
+ * expressible play: no row.  Per row (every array optional, NULL = not
+ * wanted): row_env i32 = e; codes i16[2] = (c1, c2), c2 = 0 for a one-move
+ * play; feat f32[198] = narde_observe's tesauro198 after that step (the
+ * mover is not flipped after a terminal step); obs i32[24] and reward i8 =
+ * that step's outputs (reward != 0 = terminated).  cap = rows the arrays
+ * hold: rows >= cap are not written and nothing past cap rows is touched;
+ * offsets always holds the true counts, so offsets[B] > cap tells the caller
+ * it overflowed.  cap = 0 with every row array NULL counts only.  feat and
+ * obs must be 16-byte aligned.  Stream-ordered, no allocation, no
+ * synchronise: graph-capturable.  B x 1152 must stay below 2^31. */
+int narde_afterstates(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                      int32_t *row_env, int16_t *codes, float *feat, int32_t *obs, int8_t *reward,
+                      void *stream);
+
+/* Value-greedy play over narde_afterstates' rows: one row per env from
+ * value[r * ld_value] (a value network's output for feat row r).
+ * perspective 0: the values are the mover's -- the largest; perspective 1:
+ * they are white's (the README's reward, "+1 if WHITE wins") -- the largest
+ * when white moves, the smallest when black does (read from the record, so
+ * call it before the step).  The lowest row on ties; a NaN as torch.max /
+ * torch.min(dim) take it.  Rows >= cap are ignored.  epsilon f32 / tag i64
+ * device scalars (epsilon NULL = greedy): when the env's explore draw
+ * Philox4x32-10({*tag, env, 0, 5}, seed) r0 < *epsilon * 2^32, the row is
+ * offsets[e] + mulhi(r1, count) instead.  actions i16[B][2] = the row's
+ * codes, ready for narde_step; row i32[B] (optional) = the row, -1 and
+ * actions (0, 0) for an env with no row. */
+int narde_afterstate_pick(narde_env *env, const int32_t *offsets, const int16_t *codes, int64_t cap,
+                          const float *value, int64_t ld_value, int perspective, const float *epsilon,
+                          uint64_t seed, const int64_t *tag, int16_t *actions, int32_t *row,
+                          void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry
