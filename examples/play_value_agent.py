@@ -4,9 +4,11 @@
 with --weights) scores the afterstates of every env's roll and both sides
 play the best one for them (white the largest value, black the smallest:
 the README's reward is "+1 if WHITE wins").  Everything per ply runs on the
-device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step.
+device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step
+(--rules full4: whole turns under the real rules, four sub-moves on doubles:
+turn_afterstates -> net -> pick_turn -> step).
 
-  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE]
+  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4]
 """
 import argparse
 import os
@@ -26,13 +28,13 @@ def make_net(seed, device):
     return net.to(device).eval()
 
 
-def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda"):
+def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2"):
     import torch
 
     from gym_narde.value_play import ValuePlayer
     from gym_narde.vector import VecNardeEnv
 
-    env = VecNardeEnv(envs, device=device, seed=seed)
+    env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
     net = make_net(seed, env.device)
     if weights:
         net.load_state_dict(torch.load(weights, map_location=env.device))
@@ -57,5 +59,6 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--epsilon", type=float, default=0.0)
     ap.add_argument("--weights", default=None)
+    ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
     a = ap.parse_args()
-    main(a.envs, a.plies, a.seed, a.epsilon, a.weights)
+    main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules)

@@ -53,6 +53,42 @@ struct alignas(16) AftStage {  // per wave, fill pass
   float rows[kAftRows * 198 + 4];  // the staged rows, 8 B in at an odd first row
 };
 
+// The 198-float rows of the nnew records a chunk left in S.rec (by rank) ->
+// feat rows R0 .. R0 + nnew - 1, below cap: staged kAftRows at a time
+// (tes_stage_quarter) and streamed out as one contiguous byte run.  All
+// lanes of the wave call it with the same arguments.
+__device__ __forceinline__ void aft_flush_feat(float* __restrict__ feat, int64_t cap, int64_t Rbase, int nnew,
+                                               AftStage& S, int lane) {
+  wave_lds_handoff();  // the records, to the lanes that stage them
+  for (int g0 = 0; g0 < nnew; g0 += kAftRows) {
+    const int64_t R0 = Rbase + g0;
+    const int64_t room = cap - R0;
+    const int want = min(kAftRows, nnew - g0);
+    const int nr = room < (int64_t)want ? (int)room : want;
+    if (nr <= 0) break;  // wave-uniform: the rest is past cap
+    // a row is 792 B: an odd first row starts 8 B into a 16-B piece, and
+    // so do the staged rows, so every piece is aligned on both sides
+    const int ph = (int)(R0 & 1) * 2;
+    const int le = lane & 15;  // (kAftRows of the 16 row slots of tes_stage_rows' lane layout)
+    if (le < nr) tes_stage_quarter(S.rec[g0 + le][0], S.rec[g0 + le][1], lane >> 4, S.rows + ph + le * 198);
+    wave_lds_handoff();
+    const uint32_t lo = 4u * (uint32_t)ph, hi = lo + (uint32_t)nr * kTesRowB;
+    const float4* src = reinterpret_cast<const float4*>(S.rows);
+    float4* dst = reinterpret_cast<float4*>(feat + R0 * 198 - ph);
+    for (uint32_t k = (uint32_t)lane; 16u * k < hi; k += 64u) {
+      const uint32_t b0 = 16u * k;
+      if (b0 >= lo && b0 + 16u <= hi) {
+        dst[k] = src[k];
+      } else {  // the run starts or ends inside this piece: its 8-B half
+        const int h = b0 < lo ? 2 : 0;
+        *reinterpret_cast<float2*>(reinterpret_cast<float*>(dst + k) + h) =
+            *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(src + k) + h);
+      }
+    }
+    wave_lds_handoff();  // the next rows are staged behind these reads
+  }
+}
+
 // env e's rows (all lanes of the wave call it with the same e); returns the
 // number of rows.  kFill: write them from row a.offsets[e] on, below a.cap.
 template <bool kFill>
@@ -137,36 +173,7 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
           if (a.obs) store_obs(a.obs, (size_t)R, c);
         }
       }
-      if (a.feat) {
-        wave_lds_handoff();  // the records, to the lanes that stage them
-        for (int g0 = 0; g0 < nnew; g0 += kAftRows) {
-          const int64_t R0 = row0 + nkept + g0;
-          const int64_t room = a.cap - R0;
-          const int want = min(kAftRows, nnew - g0);
-          const int nr = room < (int64_t)want ? (int)room : want;
-          if (nr <= 0) break;  // wave-uniform: the rest is past cap
-          // a row is 792 B: an odd first row starts 8 B into a 16-B piece, and
-          // so do the staged rows, so every piece is aligned on both sides
-          const int ph = (int)(R0 & 1) * 2;
-          const int le = lane & 15;  // (kAftRows of the 16 row slots of tes_stage_rows' lane layout)
-          if (le < nr) tes_stage_quarter(S->rec[g0 + le][0], S->rec[g0 + le][1], lane >> 4, S->rows + ph + le * 198);
-          wave_lds_handoff();
-          const uint32_t lo = 4u * (uint32_t)ph, hi = lo + (uint32_t)nr * kTesRowB;
-          const float4* src = reinterpret_cast<const float4*>(S->rows);
-          float4* dst = reinterpret_cast<float4*>(a.feat + R0 * 198 - ph);
-          for (uint32_t k = (uint32_t)lane; 16u * k < hi; k += 64u) {
-            const uint32_t b0 = 16u * k;
-            if (b0 >= lo && b0 + 16u <= hi) {
-              dst[k] = src[k];
-            } else {  // the run starts or ends inside this piece: its 8-B half
-              const int h = b0 < lo ? 2 : 0;
-              *reinterpret_cast<float2*>(reinterpret_cast<float*>(dst + k) + h) =
-                  *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(src + k) + h);
-            }
-          }
-          wave_lds_handoff();  // the next rows are staged behind these reads
-        }
-      }
+      if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + nkept, nnew, *S, lane);
     }
     nkept += nnew;
     wave_lds_handoff();  // the keys, to the next chunk
@@ -271,14 +278,11 @@ __global__ void __launch_bounds__(kAftScanBlock) k_aft_scan(int32_t* __restrict_
 // explore draw Philox4x32-10({*tag, env, 0, 5}, seed) r0 < epsilon * 2^32
 // (the policy kernels' decision) takes row offsets[e] + mulhi(r1, count)
 // instead.  An env with no row: row -1, actions (0, 0).  One lane per env.
-__global__ void __launch_bounds__(kBlock) k_aft_pick(Planes pl, int n, const int32_t* __restrict__ offsets,
-                                                     const int16_t* __restrict__ codes, int64_t cap,
-                                                     const float* __restrict__ value, int64_t ld, int perspective,
-                                                     const float* __restrict__ eps_p,
-                                                     const int64_t* __restrict__ tag_p, uint32_t k0, uint32_t k1,
-                                                     int16_t* __restrict__ actions, int32_t* __restrict__ row_out) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
+// (aft_pick_row: the selection, shared with k_turn_pick.)
+__device__ __forceinline__ int64_t aft_pick_row(const Planes& pl, int i, const int32_t* __restrict__ offsets,
+                                                int64_t cap, const float* __restrict__ value, int64_t ld,
+                                                int perspective, const float* __restrict__ eps_p,
+                                                const int64_t* __restrict__ tag_p, uint32_t k0, uint32_t k1) {
   const int64_t r0 = offsets[i];
   const int64_t r1 = min((int64_t)offsets[i + 1], cap);
   const int cnt = r1 > r0 ? (int)(r1 - r0) : 0;
@@ -303,6 +307,18 @@ __global__ void __launch_bounds__(kBlock) k_aft_pick(Planes pl, int n, const int
       row = r0 + bi;
     }
   }
+  return row;
+}
+
+__global__ void __launch_bounds__(kBlock) k_aft_pick(Planes pl, int n, const int32_t* __restrict__ offsets,
+                                                     const int16_t* __restrict__ codes, int64_t cap,
+                                                     const float* __restrict__ value, int64_t ld, int perspective,
+                                                     const float* __restrict__ eps_p,
+                                                     const int64_t* __restrict__ tag_p, uint32_t k0, uint32_t k1,
+                                                     int16_t* __restrict__ actions, int32_t* __restrict__ row_out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const int64_t row = aft_pick_row(pl, i, offsets, cap, value, ld, perspective, eps_p, tag_p, k0, k1);
   const uint32_t pair = row >= 0 ? reinterpret_cast<const uint32_t*>(codes)[row] : 0u;
   reinterpret_cast<uint32_t*>(actions)[i] = pair;
   if (row_out) row_out[i] = (int32_t)row;

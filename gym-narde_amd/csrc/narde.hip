@@ -62,6 +62,7 @@ int fail(int code, const char* fmt, ...) {
 #include "kernels_rollout.h"
 #include "kernels_agent.h"
 #include "kernels_afterstates.h"
+#include "kernels_turn_afterstates.h"
 
 namespace {
 
@@ -87,6 +88,10 @@ struct narde_env {
   uint8_t* d_out;
   hipStream_t hstream;
   size_t stage_bytes;
+  // narde_turn_afterstates' workspace, made on its first call: the overflow
+  // list [1 + n] and the overflow launches' frontier slab
+  int32_t* turn_ovf;
+  uint8_t* turn_slab;
 };
 
 namespace {
@@ -213,6 +218,7 @@ int narde_destroy(narde_env* e) {
   (void)hipFree(e->pl.p0); (void)hipFree(e->pl.p1); (void)hipFree(e->pl.stats);
   (void)hipFree(e->hpl.p0); (void)hipFree(e->hpl.p1); (void)hipFree(e->hpl.stats);
   (void)hipFree(e->d_in); (void)hipFree(e->d_out);
+  (void)hipFree(e->turn_ovf); (void)hipFree(e->turn_slab);
   if (e->h_in) (void)hipHostFree(e->h_in);
   if (e->h_out) (void)hipHostFree(e->h_out);
   if (e->hstream) (void)hipStreamDestroy(e->hstream);
@@ -648,6 +654,68 @@ int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* c
                                                              perspective, epsilon, tag, (uint32_t)seed,
                                                              (uint32_t)(seed >> 32), actions, row);
   return check_launch("k_aft_pick");
+}
+
+int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
+                           int8_t* play, float* feat, int32_t* obs, int8_t* reward, void* stream) {
+  if (!e || !offsets) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (e->n * (int64_t)NARDE_TURN_AFT_MAX >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", NARDE_TURN_AFT_MAX);
+  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
+      (reinterpret_cast<uintptr_t>(play) % 8))
+    return fail(NARDE_EINVAL, "feat and obs must be 16-B aligned, play 8-B aligned");
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (!e->turn_slab) {
+    // the workspace belongs to the handle and is made once, outside capture
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      return fail(NARDE_EINVAL, "the first narde_turn_afterstates call of a handle allocates its workspace: "
+                                "make it outside stream capture");
+    hipError_t err = hipMalloc(&e->turn_ovf, (size_t)(e->n + 1) * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc(&e->turn_slab, (size_t)kTurnOvfWaves * kTurnSlabWave);
+    if (err != hipSuccess) {
+      (void)hipFree(e->turn_ovf);
+      (void)hipFree(e->turn_slab);
+      e->turn_ovf = nullptr;
+      e->turn_slab = nullptr;
+      return fail(NARDE_ENOMEM, "turn afterstate workspace: %s", hipGetErrorString(err));
+    }
+  }
+  TurnArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, play, feat, obs, reward, e->turn_ovf,
+             e->turn_slab};
+  const int cw = kTurnCountBlock / 64, fw = kTurnFillBlock / 64;
+  HIP_TRY(hipMemsetAsync(e->turn_ovf, 0, sizeof(int32_t), st));
+  k_turn_count<<<(unsigned)((e->n + cw - 1) / cw), kTurnCountBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_count")) return rc;
+  k_turn_overflow<false><<<kTurnOvfWaves, 64, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_overflow<count>")) return rc;
+  k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
+  if (const int rc = check_launch("k_aft_scan")) return rc;
+  if (cap == 0 || !(row_env || play || feat || obs || reward)) return NARDE_OK;
+  k_turn_fill<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_fill")) return rc;
+  k_turn_overflow<true><<<kTurnOvfWaves, 64, 0, st>>>(a);
+  return check_launch("k_turn_overflow<fill>");
+}
+
+int narde_turn_pick(narde_env* e, const int32_t* offsets, const int8_t* play, int64_t cap, const float* value,
+                    int64_t ld_value, int perspective, const float* epsilon, uint64_t seed, const int64_t* tag,
+                    int8_t* out_play, int32_t* row, void* stream) {
+  if (!e || !offsets || !play || !value || !out_play) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (perspective != 0 && perspective != 1)
+    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if (epsilon && !tag) return fail(NARDE_EINVAL, "exploration needs a tag");
+  if ((reinterpret_cast<uintptr_t>(play) % 8) || (reinterpret_cast<uintptr_t>(out_play) % 8))
+    return fail(NARDE_EINVAL, "play and out_play must be 8-B aligned");
+  DeviceGuard dg(e->device);
+  k_turn_pick<<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(e->pl, (int)e->n, offsets, play, cap, value, ld_value,
+                                                              perspective, epsilon, tag, (uint32_t)seed,
+                                                              (uint32_t)(seed >> 32), out_play, row);
+  return check_launch("k_turn_pick");
 }
 
 int narde_policy_masked_argmax576(int device, const float* q, int64_t ldq, const uint64_t* mask, int64_t n,

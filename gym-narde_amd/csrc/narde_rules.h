@@ -2190,4 +2190,145 @@ NARDE_FN void env_ply_full(Side& s, int4& st, const uint32_t r[4], uint32_t env,
                     });
 }
 
+// ================================================= FULL4 turn afterstates
+// The distinct positions a whole FULL4 turn can leave
+// (VecNardeEnv.turn_afterstates).  Level k = the
+// distinct positions k legal single-die sub-moves reach (legal1 with the
+// turn's head limit; two different dice: each die once, so a level-1 node
+// also carries which die is left); M = the deepest non-empty level, and the
+// rows are level M -- two different dice with M = 1: the higher die's nodes
+// if it has any.  A position that lies on no M-play has no child at the next
+// level, so no f4_keep search is needed.  Parents are expanded in order,
+// children in list order (higher die first, source ascending), the first
+// occurrence kept: a node's path is the lexicographically smallest play
+// prefix that reaches it, and level M comes out in the order of each row's
+// first play.
+//
+// A node is its path word: byte k = the source of sub-move k (0xFF: none);
+// bit 7 of byte 0: two different dice and the LOWER die went first.
+constexpr int kTurnAftMax = 5220;  // rows (and nodes of any level) per env: DESIGN.md section 14.2
+constexpr uint32_t kTurnNoPath = 0xFFFFFFFFu;
+constexpr uint64_t kTurnNoKey = ~0ull;
+
+NARDE_FN int turn_path_from(uint32_t path, int k) { return (int)((path >> (8 * k)) & 31u); }
+// the die of sub-move k (doubles: dh = dl)
+NARDE_FN int turn_path_die(uint32_t path, int k, int dh, int dl) {
+  const bool low_first = ((path >> 7) & 1u) != 0u;
+  return ((k == 0) == low_first) ? dl : dh;
+}
+NARDE_FN uint32_t turn_child_path(uint32_t path, int k, int src, bool low_first) {
+  const uint32_t b = (uint32_t)src | (low_first ? 0x80u : 0u);
+  return (path & ~(0xFFu << (8 * k))) | (b << (8 * k));
+}
+
+// the first n sub-moves of path applied to s (straight-line)
+NARDE_FN void turn_path_apply(Side& s, uint32_t path, int n, int dh, int dl) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) apply_die_if(s, turn_path_from(path, k), turn_path_die(path, k, dh, dl), k < n);
+}
+
+// Board + off identity of the node the first n sub-moves of path reach, as
+// play_key extended to a turn: the opponent is fixed, so the position is the
+// root less one checker at each source plus one at each target ('off' =
+// point 24); a point that is both cancels (pairwise: the rest are S \ T and
+// T \ S as multisets, whatever the pairing), and two nodes are the same
+// position iff the sorted remainders agree -- 4 + 4 points of 5 bits, 31 for
+// a missing one.  Head moves used are the sources equal to 23 (a target is
+// never 23, so they never cancel).  die_left: bit 40 = the lower die went
+// first (level 1 of two different dice, where the die left is part of the
+// node).
+NARDE_FN void turn_cswap(uint32_t& a, uint32_t& b) {
+  const uint32_t lo = a < b ? a : b, hi = a < b ? b : a;
+  a = lo;
+  b = hi;
+}
+NARDE_FN uint64_t turn_path_key(uint32_t path, int n, int dh, int dl, bool die_left) {
+  uint32_t s0 = 31u, s1 = 31u, s2 = 31u, s3 = 31u, t0 = 31u, t1 = 31u, t2 = 31u, t3 = 31u;
+#define NARDE_TK_LOAD(k, sk, tk)                                    \
+  if ((k) < n) {                                                    \
+    const int f = turn_path_from(path, (k));                        \
+    const int d = turn_path_die(path, (k), dh, dl);                 \
+    sk = (uint32_t)f;                                               \
+    tk = f < d ? (uint32_t)OFF : (uint32_t)(f - d);                 \
+  }
+  NARDE_TK_LOAD(0, s0, t0)
+  NARDE_TK_LOAD(1, s1, t1)
+  NARDE_TK_LOAD(2, s2, t2)
+  NARDE_TK_LOAD(3, s3, t3)
+#undef NARDE_TK_LOAD
+#define NARDE_TK_CANCEL(sk, tk)                  \
+  {                                              \
+    const bool c = sk != 31u && sk == tk;        \
+    sk = c ? 31u : sk;                           \
+    tk = c ? 31u : tk;                           \
+  }
+  // a sub-move's source only meets the target of an EARLIER sub-move
+  // (targets lie below their sources and a later sub-move's source is
+  // where an earlier one landed), but every pair is cheap enough
+  NARDE_TK_CANCEL(s0, t1) NARDE_TK_CANCEL(s0, t2) NARDE_TK_CANCEL(s0, t3)
+  NARDE_TK_CANCEL(s1, t0) NARDE_TK_CANCEL(s1, t2) NARDE_TK_CANCEL(s1, t3)
+  NARDE_TK_CANCEL(s2, t0) NARDE_TK_CANCEL(s2, t1) NARDE_TK_CANCEL(s2, t3)
+  NARDE_TK_CANCEL(s3, t0) NARDE_TK_CANCEL(s3, t1) NARDE_TK_CANCEL(s3, t2)
+#undef NARDE_TK_CANCEL
+  turn_cswap(s0, s1); turn_cswap(s2, s3); turn_cswap(s0, s2); turn_cswap(s1, s3); turn_cswap(s1, s2);
+  turn_cswap(t0, t1); turn_cswap(t2, t3); turn_cswap(t0, t2); turn_cswap(t1, t3); turn_cswap(t1, t2);
+  const uint32_t S = s0 | (s1 << 5) | (s2 << 10) | (s3 << 15);
+  const uint32_t T = t0 | (t1 << 5) | (t2 << 10) | (t3 << 15);
+  const uint64_t die = (die_left && ((path >> 7) & 1u)) ? (1ull << 40) : 0ull;
+  return (uint64_t)S | ((uint64_t)T << 20) | die;
+}
+
+// the play of a level-n path as narde_step_full reads it: byte 2k = from,
+// 2k + 1 = die, 0xFF (-1) behind the last sub-move
+NARDE_FN uint64_t turn_path_play(uint32_t path, int n, int dh, int dl) {
+  uint64_t pw = ~0ull;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < n) pw = played_set(pw, k, turn_path_from(path, k), turn_path_die(path, k, dh, dl));
+  return pw;
+}
+
+struct TurnRoot {
+  uint32_t low;  // the block rule's low mask: the opponent is fixed for the turn
+  int dh, dl;
+  int hmax;      // head moves a turn may make
+  int depth;     // sub-moves a turn may make: 4 on doubles, else 2
+  bool bf;       // turn_block_free
+};
+NARDE_FN TurnRoot turn_root(const Side& s, int d0, int d1) {
+  TurnRoot r;
+  r.low = block_lowmask(s.P);
+  r.dh = d0 > d1 ? d0 : d1;
+  r.dl = d0 > d1 ? d1 : d0;
+  const bool dbl = r.dh == r.dl;
+  r.hmax = (dbl && s.ft_own && (r.dh == 3 || r.dh == 4 || r.dh == 6)) ? 2 : 1;
+  r.depth = dbl ? 4 : 2;
+  r.bf = turn_block_free(s.O, s.S1o, s.P, r.low, r.dh, r.dl);
+  return r;
+}
+
+// the sub-move lists of the level-`level` node c (= the root with path
+// applied): w0, then w1, each sources | die << 24.  Doubles: one list; two
+// different dice: both at the root (higher die first), the die left at
+// level 1.
+NARDE_FN void turn_node_lists(const Side& c, uint32_t path, int level, const TurnRoot& r, uint32_t& w0, uint32_t& w1) {
+  int heads = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) heads += (k < level && turn_path_from(path, k) == 23) ? 1 : 0;
+  const uint32_t hm = heads >= r.hmax ? ~HEAD : ~0u;
+  const bool two = r.dh != r.dl && level == 0;
+  const int da = (r.dh != r.dl && level == 1) ? turn_path_die(path, 1, r.dh, r.dl) : r.dh;
+  w0 = (legal1(c, r.low, da, r.bf) & hm) | ((uint32_t)da << 24);
+  w1 = two ? ((legal1(c, r.low, r.dl, r.bf) & hm) | ((uint32_t)r.dl << 24)) : 0u;
+}
+
+// child r (list order) of a node with lists (w0, w1) at `level`
+NARDE_FN uint32_t turn_child(uint32_t path, int level, uint32_t w0, uint32_t w1, int r) {
+  const int n0 = __builtin_popcount(w0 & MASK24);
+  const bool second = r >= n0;
+  const uint32_t m = (second ? w1 : w0) & MASK24;
+  const int src = select_bit(m, second ? r - n0 : r);
+  return turn_child_path(path, level, src, level == 0 && second);
+}
+
 }  // namespace narde

@@ -67,6 +67,8 @@ SIGNATURES = {
     "narde_explore_plays": (_i32, [_vp, _vp, _vp, _u64, _vp, _vp, _i64, _vp]),
     "narde_afterstates": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_afterstate_pick": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "narde_turn_afterstates": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_turn_pick": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

@@ -6,6 +6,8 @@ scores the positions a roll can lead to -- the afterstates -- with a value
 network and plays the best one.  ValuePlayer does that for B envs at once,
 everything on the device: VecNardeEnv.afterstates() expands the roll,
 `net` scores the rows, VecNardeEnv.pick_afterstate() chooses, step() plays.
+On a rules="full4" env the rows are whole turns (turn_afterstates(),
+pick_turn()): four sub-moves on doubles, the max-dice-used rule.
 """
 
 
@@ -21,8 +23,6 @@ class ValuePlayer:
 
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
-        if env.full:
-            raise ValueError('ValuePlayer is rules="ref2" only')
         self.env, self.net, self.perspective = env, net, perspective
 
     def values(self, aft):
@@ -46,12 +46,18 @@ class ValuePlayer:
         """One ply for every env: the next step's dice, their afterstates, the
         values, the pick, the step.  Returns (obs, reward, terminated,
         truncated, info, aft, values, actions); an env with no expressible
-        play steps with (0, 0), which moves nothing."""
+        play steps with (0, 0), which moves nothing (rules="full4": actions
+        are (B,4,2) plays, all -1 for an env that has to pass)."""
         env = self.env
         dice = env.dice()
-        aft = env.afterstates(dice)
-        values = self.values(aft)
-        actions, row = env.pick_afterstate(aft, values, self.perspective, epsilon, tag, seed)
+        if env.full:
+            aft = env.turn_afterstates(dice)
+            values = self.values(aft)
+            actions, row = env.pick_turn(aft, values, self.perspective, epsilon, tag, seed)
+        else:
+            aft = env.afterstates(dice)
+            values = self.values(aft)
+            actions, row = env.pick_afterstate(aft, values, self.perspective, epsilon, tag, seed)
         obs, reward, terminated, truncated, info = env.step(actions)
         info = dict(info, dice=dice, row=row)
         return obs, reward, terminated, truncated, info, aft, values, actions

@@ -118,6 +118,9 @@ PERSPECTIVES = {"mover": 0, "white": 1}
 # offsets[e + 1] - 1); cap = the rows the arrays hold -- offsets[B] > cap
 # means the call overflowed and the rows from cap on were not written
 Afterstates = collections.namedtuple("Afterstates", "offsets row_env codes feat obs reward cap")
+# VecNardeEnv.turn_afterstates' result (rules="full4"): the same CSR rows with
+# play (R,4,2) int8 (from, die) in place of the action codes
+TurnAfterstates = collections.namedtuple("TurnAfterstates", "offsets row_env play feat obs reward cap")
 
 
 class VecNardeEnv:
@@ -428,6 +431,92 @@ class VecNardeEnv:
                          _lib.ptr(tag), _lib.ptr(actions), _lib.ptr(row), self._s())
         self._keep = (v, epsilon, tag)
         return actions, row
+
+    def turn_afterstates(self, dice=None, cap=None, feat=True, obs=False, out=None):
+        """rules="full4": the distinct positions each env's whole turn can
+        leave (narde_turn_afterstates; four sub-moves on doubles, the
+        max-dice-used rule), for dice (B,2) or the next step's device dice.
+        Rows are ordered by the first play -- plays in lexicographic order,
+        sub-moves in list order: higher die first, source ascending -- that
+        produces each one; a pass or a die outside 1..6 gives no row.
+        Returns TurnAfterstates(offsets (B+1,) int32, row_env (R,) int32,
+        play (R,4,2) int8 (from, die), -1 padded -- feed them to step() --,
+        feat (R,198) float32 = tesauro198() after that turn, obs (R,24)
+        int32 or None, reward (R,) int8 -- 0, or 1 / 2 at a terminal
+        afterstate --, cap = R).  cap / out as afterstates(): cap None runs
+        the count pass and reads offsets[B] on the host -- the call's ONE
+        synchronise; cap given (or out) is one stream-ordered call, safe to
+        capture in a graph once the handle has made one call outside
+        capture (its workspace is allocated then)."""
+        if not self.full:
+            raise ValueError('turn_afterstates() is rules="full4" only')
+        B, t = self.num_envs, self.torch
+        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        if out is not None:
+            offsets = out.offsets
+            cap = out.cap if cap is None else int(cap)
+            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
+                                       ("play", out.play, (4, 2), t.int8), ("feat", out.feat, (198,), t.float32),
+                                       ("obs", out.obs, (24,), t.int32), ("reward", out.reward, (), t.int8)):
+                if a is None:
+                    continue
+                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
+                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
+                if not ok:
+                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
+        else:
+            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
+            if cap is None:
+                self.handle.call("narde_turn_afterstates", _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None,
+                                 None, self._s())
+                cap = int(offsets[B].item())  # the one synchronise
+            cap = int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
+            out = TurnAfterstates(offsets, mk(True, (), t.int32), mk(True, (4, 2), t.int8), mk(feat, (198,), t.float32),
+                                  mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        rows = (out.row_env, out.play, out.feat, out.obs, out.reward)
+        self.handle.call("narde_turn_afterstates", _lib.ptr(d), cap, _lib.ptr(offsets),
+                         *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
+        self._keep = (d,)
+        return out._replace(cap=cap)
+
+    def pick_turn(self, aft, values, perspective="white", epsilon=None, tag=None, seed=0):
+        """pick_afterstate() over turn_afterstates' rows (narde_turn_pick: the
+        same perspective, tie, NaN and explore-draw rules).  Returns (play
+        (B,4,2) int8 for step(), row (B,) int32; -1 and an all -1 play for
+        an env with no row)."""
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        if not self.full:
+            raise ValueError('pick_turn() is rules="full4" only')
+        B, t = self.num_envs, self.torch
+        v = values
+        if v.dim() == 2 and v.shape[1] == 1:
+            v = v[:, 0]
+        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
+                or (v.shape[0] > 1 and v.stride(0) < 1)):
+            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
+        if (epsilon is None) != (tag is None):
+            raise ValueError("epsilon and tag go together")
+        if epsilon is not None:
+            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
+            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+        play = t.empty((B, 4, 2), dtype=t.int8, device=self.device)
+        row = t.empty(B, dtype=t.int32, device=self.device)
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            play.fill_(-1)
+            row.fill_(-1)
+            return play, row
+        self.handle.call("narde_turn_pick", _lib.ptr(aft.offsets), _lib.ptr(aft.play), aft.cap, _lib.ptr(v),
+                         max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
+                         _lib.ptr(tag), _lib.ptr(play), _lib.ptr(row), self._s())
+        self._keep = (v, epsilon, tag)
+        return play, row
 
     def legal_full(self, dice=None):
         """FULL4: (B,) int64 legal words (first sub-move set | max dice << 56)

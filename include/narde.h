@@ -339,6 +339,45 @@ int narde_afterstate_pick(narde_env *env, const int32_t *offsets, const int16_t 
                           uint64_t seed, const int64_t *tag, int16_t *actions, int32_t *row,
                           void *stream);
 
+/* FULL4 whole-turn afterstates: the distinct positions a whole turn can
+ * leave (four sub-moves on doubles, the max-dice-used rule), stated against
+ * or_full4_turn (oracle/narde_oracle.c).  A play is a sequence of sub-moves
+ * (from, die), each taken from C_k for the prefix before it, of length M;
+ * plays are ordered lexicographically, each sub-move in list order (higher
+ * die first, source ascending).  A play's afterstate is what
+ * narde_step_full(play, dice, autoreset = 0) leaves: the sub-moves, then
+ * _check_game_ended and the flip (the mover is not flipped after a terminal
+ * turn).  An env's rows are its DISTINCT afterstates (equal board and off
+ * counts are the same), ordered by the first play that produces each one;
+ * that play is the row's.  The order is the same on every call (no atomic
+ * decides it).  M = 0 (a pass) or a die outside 1..6: no row.  The result is
+ * exact for every position: a row count per env never exceeds
+ * NARDE_TURN_AFT_MAX (DESIGN.md section 14.2 derives it) and none is
+ * truncated.
+ * offsets i32[B + 1] CSR as narde_afterstates.  Per row (every array
+ * optional): row_env i32; play i8[4][2] = (from, die), -1 padding, ready for
+ * narde_step_full; feat f32[198] = narde_observe's tesauro198 after that
+ * turn; obs i32[24]; reward i8 (!= 0 = terminated).  cap clamps what is
+ * written, never what offsets holds; nothing past cap rows is touched;
+ * cap = 0 with every row array NULL counts only.  dice NULL = the next
+ * step's device dice.  feat and obs 16-byte, play 8-byte aligned.
+ * Stream-ordered, no synchronise, graph-capturable; the handle's workspace
+ * (11 MB) is allocated by the handle's first call, which must be made
+ * outside capture.  B x NARDE_TURN_AFT_MAX must stay below 2^31. */
+#define NARDE_TURN_AFT_MAX 5220
+int narde_turn_afterstates(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                           int32_t *row_env, int8_t *play, float *feat, int32_t *obs, int8_t *reward,
+                           void *stream);
+
+/* narde_afterstate_pick over narde_turn_afterstates' rows (the same
+ * perspective, tie, NaN and explore-draw rules; one shared selection):
+ * out_play i8[B][4][2] = the row's play, all -1 for an env with no row,
+ * ready for narde_step_full; row i32[B] (optional).  play and out_play
+ * 8-byte aligned. */
+int narde_turn_pick(narde_env *env, const int32_t *offsets, const int8_t *play, int64_t cap,
+                    const float *value, int64_t ld_value, int perspective, const float *epsilon,
+                    uint64_t seed, const int64_t *tag, int8_t *out_play, int32_t *row, void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry
