@@ -1,6 +1,7 @@
-// kernels_turn_afterstates.h -- FULL4 whole-turn afterstates and their value-greedy pick
-// Part of the one translation unit narde.hip (included there, in order);
-// not a standalone header.
+// kernels_turn_afterstates.h -- FULL4 whole-turn afterstates: the level walk
+// Part of the one translation unit narde.hip (included there, in order,
+// behind kernels_rows.h: the row set, the scan, the pick and the wave
+// helpers are there); not a standalone header.
 #pragma once
 
 namespace {
@@ -104,6 +105,9 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         turn_node_lists(c, path, level, r, w0, w1);
         w0 = act ? w0 : 0u;
         w1 = act ? w1 : 0u;
+        // (wave_scan_incl, and below the earlier-lane key loop and the row
+        // stores, written out: through kernels_rows.h's helpers
+        // k_turn_overflow measured 1 % slower, MEASUREMENT_LOG M.27)
         int inc = __builtin_popcount(w0 & MASK24) + __builtin_popcount(w1 & MASK24);
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -121,9 +125,7 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         const bool act = c0 + lane < total;
         const int j = act ? c0 + lane : 0;
         // the parent of child j: the first whose inclusive sum exceeds j
-        int pi = 0;
-#pragma unroll
-        for (int st = 32; st > 0; st >>= 1) pi += (int)L.incl[pi + st - 1] <= j ? st : 0;
+        const int pi = wave_owner_of(L.incl, j);
         const int excl = pi ? (int)L.incl[pi - 1] : 0;
         const uint32_t cp = turn_child(pcur[p0 + pi], level, L.w0[pi], L.w1[pi], j - excl);
         const uint64_t key = act ? turn_path_key(cp, level + 1, r.dh, r.dl, two && level == 0) : kTurnNoKey;
@@ -142,9 +144,8 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
           dupe |= q < lane && qlo == (uint32_t)klo && qhi == (uint32_t)khi;
         }
         const bool keep = act && !dupe;
-        const uint64_t bal = __ballot(keep);
-        const int rank = __builtin_popcountll(bal & ((1ull << lane) - 1ull));
-        const int nnew = __builtin_popcountll(bal);
+        int nnew;
+        const int rank = wave_keep_rank(keep, lane, nnew);
         if (nnext + nnew > room) return -1;  // wave-uniform: the level does not fit
         if (keep) {
           knxt[nnext + rank] = key;
@@ -254,21 +255,6 @@ __global__ void __launch_bounds__(64) k_turn_overflow(TurnArgs a) {
     if (!kFill && (threadIdx.x & 63) == 0) a.offsets[e + 1] = cnt < 0 ? 0 : cnt;
     wave_lds_handoff();
   }
-}
-
-// k_aft_pick over turn rows: the row by aft_pick_row, its play (all -1 for
-// an env with no row).  One lane per env.
-__global__ void __launch_bounds__(kBlock) k_turn_pick(Planes pl, int n, const int32_t* __restrict__ offsets,
-                                                      const int8_t* __restrict__ play, int64_t cap,
-                                                      const float* __restrict__ value, int64_t ld, int perspective,
-                                                      const float* __restrict__ eps_p,
-                                                      const int64_t* __restrict__ tag_p, uint32_t k0, uint32_t k1,
-                                                      int8_t* __restrict__ out_play, int32_t* __restrict__ row_out) {
-  const int i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= n) return;
-  const int64_t row = aft_pick_row(pl, i, offsets, cap, value, ld, perspective, eps_p, tag_p, k0, k1);
-  reinterpret_cast<uint64_t*>(out_play)[i] = row >= 0 ? reinterpret_cast<const uint64_t*>(play)[row] : ~0ull;
-  if (row_out) row_out[i] = (int32_t)row;
 }
 
 }  // namespace

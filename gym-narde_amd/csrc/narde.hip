@@ -17,8 +17,12 @@
 //                       and k_rollout_pp_full (FULL4)
 //   kernels_agent.h     observations, move masks, the policy kernel, the DQN
 //                       transition
-//   kernels_afterstates.h  afterstate expansion (count, scan, fill) and the
-//                       value-greedy pick
+//   kernels_rows.h      afterstate rows, what both rule sets share: the wave
+//                       helpers, the row stores, k_aft_scan, k_aft_pick
+//   kernels_afterstates.h  REF2 afterstates: the play enumeration
+//                       (k_aft_count, k_aft_fill)
+//   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
+//                       (k_turn_count, k_turn_fill, k_turn_overflow)
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip).
 #include <hip/hip_runtime.h>
@@ -61,6 +65,7 @@ int fail(int code, const char* fmt, ...) {
 #include "kernels_full4.h"
 #include "kernels_rollout.h"
 #include "kernels_agent.h"
+#include "kernels_rows.h"
 #include "kernels_afterstates.h"
 #include "kernels_turn_afterstates.h"
 
@@ -139,6 +144,43 @@ bool valid_position(const int8_t* board, const uint8_t* off, const uint8_t* ft, 
   if (player && player[i] != 1 && player[i] != -1) return false;
   (void)ft;
   return true;
+}
+
+// The two afterstate expansions' (narde_afterstates, narde_turn_afterstates)
+// argument checks.  max_rows: the kind's rows-per-env bound; column: its
+// action column, `align`-byte words; misaligned: the alignment error's text.
+int check_expand(const narde_env* e, int64_t cap, const int32_t* offsets, int max_rows, const float* feat,
+                 const int32_t* obs, const void* column, unsigned align, const char* misaligned) {
+  if (!e || !offsets) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (e->n * (int64_t)max_rows >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", max_rows);
+  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
+      (reinterpret_cast<uintptr_t>(column) % align))
+    return fail(NARDE_EINVAL, "%s", misaligned);
+  return NARDE_OK;
+}
+
+// The two picks (narde_afterstate_pick, narde_turn_pick): the checks and the
+// launch of k_aft_pick over the kind's action column of words W (kNoRow for
+// an env with no row).  kernel, misaligned: the kind's error texts.
+template <typename W, int kNoRow>
+int pick_rows(narde_env* e, const int32_t* offsets, const void* column, int64_t cap, const float* value,
+              int64_t ld_value, int perspective, const float* epsilon, uint64_t seed, const int64_t* tag, void* out,
+              int32_t* row, void* stream, const char* kernel, const char* misaligned) {
+  if (!e || !offsets || !column || !value || !out) return fail(NARDE_EINVAL, "NULL argument");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (perspective != 0 && perspective != 1)
+    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if (epsilon && !tag) return fail(NARDE_EINVAL, "exploration needs a tag");
+  if ((reinterpret_cast<uintptr_t>(column) % sizeof(W)) || (reinterpret_cast<uintptr_t>(out) % sizeof(W)))
+    return fail(NARDE_EINVAL, "%s", misaligned);
+  DeviceGuard dg(e->device);
+  k_aft_pick<W, kNoRow><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(
+      e->pl, (int)e->n, offsets, static_cast<const W*>(column), cap, value, ld_value, perspective, epsilon, tag,
+      (uint32_t)seed, (uint32_t)(seed >> 32), static_cast<W*>(out), row);
+  return check_launch(kernel);
 }
 
 }  // namespace
@@ -619,13 +661,9 @@ int narde_explore_plays(narde_env* e, const uint8_t* dice, const float* epsilon,
 
 int narde_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
                       int16_t* codes, float* feat, int32_t* obs, int8_t* reward, void* stream) {
-  if (!e || !offsets) return fail(NARDE_EINVAL, "NULL argument");
-  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
-  if (e->n * kAftMaxPlays >= (int64_t(1) << 31))
-    return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", kAftMaxPlays);
-  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
-      (reinterpret_cast<uintptr_t>(codes) % 4))
-    return fail(NARDE_EINVAL, "feat and obs must be 16-B aligned, codes 4-B aligned");
+  if (const int rc = check_expand(e, cap, offsets, kAftMaxPlays, feat, obs, codes, 4,
+                                  "feat and obs must be 16-B aligned, codes 4-B aligned"))
+    return rc;
   DeviceGuard dg(e->device);
   AftArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, feat, obs, reward};
   const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
@@ -641,30 +679,16 @@ int narde_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* o
 int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* codes, int64_t cap,
                           const float* value, int64_t ld_value, int perspective, const float* epsilon,
                           uint64_t seed, const int64_t* tag, int16_t* actions, int32_t* row, void* stream) {
-  if (!e || !offsets || !codes || !value || !actions) return fail(NARDE_EINVAL, "NULL argument");
-  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
-  if (perspective != 0 && perspective != 1)
-    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
-  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
-  if (epsilon && !tag) return fail(NARDE_EINVAL, "exploration needs a tag");
-  if ((reinterpret_cast<uintptr_t>(codes) % 4) || (reinterpret_cast<uintptr_t>(actions) % 4))
-    return fail(NARDE_EINVAL, "codes and actions must be 4-B aligned");
-  DeviceGuard dg(e->device);
-  k_aft_pick<<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(e->pl, (int)e->n, offsets, codes, cap, value, ld_value,
-                                                             perspective, epsilon, tag, (uint32_t)seed,
-                                                             (uint32_t)(seed >> 32), actions, row);
-  return check_launch("k_aft_pick");
+  // a row's two codes are one 32-bit word; no row: (0, 0)
+  return pick_rows<uint32_t, 0>(e, offsets, codes, cap, value, ld_value, perspective, epsilon, seed, tag, actions,
+                                 row, stream, "k_aft_pick", "codes and actions must be 4-B aligned");
 }
 
 int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
                            int8_t* play, float* feat, int32_t* obs, int8_t* reward, void* stream) {
-  if (!e || !offsets) return fail(NARDE_EINVAL, "NULL argument");
-  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
-  if (e->n * (int64_t)NARDE_TURN_AFT_MAX >= (int64_t(1) << 31))
-    return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", NARDE_TURN_AFT_MAX);
-  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
-      (reinterpret_cast<uintptr_t>(play) % 8))
-    return fail(NARDE_EINVAL, "feat and obs must be 16-B aligned, play 8-B aligned");
+  if (const int rc = check_expand(e, cap, offsets, NARDE_TURN_AFT_MAX, feat, obs, play, 8,
+                                  "feat and obs must be 16-B aligned, play 8-B aligned"))
+    return rc;
   DeviceGuard dg(e->device);
   hipStream_t st = (hipStream_t)stream;
   if (!e->turn_slab) {
@@ -703,19 +727,9 @@ int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32
 int narde_turn_pick(narde_env* e, const int32_t* offsets, const int8_t* play, int64_t cap, const float* value,
                     int64_t ld_value, int perspective, const float* epsilon, uint64_t seed, const int64_t* tag,
                     int8_t* out_play, int32_t* row, void* stream) {
-  if (!e || !offsets || !play || !value || !out_play) return fail(NARDE_EINVAL, "NULL argument");
-  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
-  if (perspective != 0 && perspective != 1)
-    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
-  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
-  if (epsilon && !tag) return fail(NARDE_EINVAL, "exploration needs a tag");
-  if ((reinterpret_cast<uintptr_t>(play) % 8) || (reinterpret_cast<uintptr_t>(out_play) % 8))
-    return fail(NARDE_EINVAL, "play and out_play must be 8-B aligned");
-  DeviceGuard dg(e->device);
-  k_turn_pick<<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(e->pl, (int)e->n, offsets, play, cap, value, ld_value,
-                                                              perspective, epsilon, tag, (uint32_t)seed,
-                                                              (uint32_t)(seed >> 32), out_play, row);
-  return check_launch("k_turn_pick");
+  // a row's (4,2) int8 play is one 64-bit word; no row: all -1
+  return pick_rows<uint64_t, -1>(e, offsets, play, cap, value, ld_value, perspective, epsilon, seed, tag, out_play,
+                                    row, stream, "k_turn_pick", "play and out_play must be 8-B aligned");
 }
 
 int narde_policy_masked_argmax576(int device, const float* q, int64_t ldq, const uint64_t* mask, int64_t n,

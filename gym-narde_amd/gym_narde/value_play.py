@@ -24,6 +24,8 @@ class ValuePlayer:
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
         self.env, self.net, self.perspective = env, net, perspective
+        self._expand, self._pick = ((env.turn_afterstates, env.pick_turn) if env.full else
+                                    (env.afterstates, env.pick_afterstate))
 
     def values(self, aft):
         """net(feat), with the rows that end the game set to their known
@@ -50,14 +52,9 @@ class ValuePlayer:
         are (B,4,2) plays, all -1 for an env that has to pass)."""
         env = self.env
         dice = env.dice()
-        if env.full:
-            aft = env.turn_afterstates(dice)
-            values = self.values(aft)
-            actions, row = env.pick_turn(aft, values, self.perspective, epsilon, tag, seed)
-        else:
-            aft = env.afterstates(dice)
-            values = self.values(aft)
-            actions, row = env.pick_afterstate(aft, values, self.perspective, epsilon, tag, seed)
+        aft = self._expand(dice)
+        values = self.values(aft)
+        actions, row = self._pick(aft, values, self.perspective, epsilon, tag, seed)
         obs, reward, terminated, truncated, info = env.step(actions)
         info = dict(info, dice=dice, row=row)
         return obs, reward, terminated, truncated, info, aft, values, actions

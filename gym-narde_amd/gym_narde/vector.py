@@ -121,6 +121,11 @@ Afterstates = collections.namedtuple("Afterstates", "offsets row_env codes feat 
 # VecNardeEnv.turn_afterstates' result (rules="full4"): the same CSR rows with
 # play (R,4,2) int8 (from, die) in place of the action codes
 TurnAfterstates = collections.namedtuple("TurnAfterstates", "offsets row_env play feat obs reward cap")
+# what differs between the two: the C entry points, the tuple, the action
+# column (field, trailing shape, torch dtype), the pick's fill for no row
+_RowKind = collections.namedtuple("_RowKind", "expand pick tuple field shape dtype no_row")
+_REF2_ROWS = _RowKind("narde_afterstates", "narde_afterstate_pick", Afterstates, "codes", (2,), "int16", 0)
+_FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAfterstates, "play", (4, 2), "int8", -1)
 
 
 class VecNardeEnv:
@@ -341,6 +346,71 @@ class VecNardeEnv:
         self._keep = (d,)
         return actions
 
+    def _expand_rows(self, k, dice, cap, feat, obs, out):
+        """afterstates() / turn_afterstates(): the rows of kind k (a _RowKind)."""
+        B, t = self.num_envs, self.torch
+        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        if out is not None:
+            offsets = out.offsets
+            cap = out.cap if cap is None else int(cap)
+            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
+                                       (k.field, getattr(out, k.field), k.shape, getattr(t, k.dtype)),
+                                       ("feat", out.feat, (198,), t.float32), ("obs", out.obs, (24,), t.int32),
+                                       ("reward", out.reward, (), t.int8)):
+                if a is None:
+                    continue
+                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
+                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
+                if not ok:
+                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
+        else:
+            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
+            if cap is None:
+                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+                cap = int(offsets[B].item())  # the one synchronise
+            cap = int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
+            out = k.tuple(offsets, mk(True, (), t.int32), mk(True, k.shape, getattr(t, k.dtype)),
+                          mk(feat, (198,), t.float32), mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        rows = (out.row_env, getattr(out, k.field), out.feat, out.obs, out.reward)
+        self.handle.call(k.expand, _lib.ptr(d), cap, _lib.ptr(offsets),
+                         *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
+        self._keep = (d,)
+        return out._replace(cap=cap)
+
+    def _pick_rows(self, k, aft, values, perspective, epsilon, tag, seed):
+        """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        B, t = self.num_envs, self.torch
+        v = values
+        if v.dim() == 2 and v.shape[1] == 1:
+            v = v[:, 0]
+        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
+                or (v.shape[0] > 1 and v.stride(0) < 1)):
+            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
+        if (epsilon is None) != (tag is None):
+            raise ValueError("epsilon and tag go together")
+        if epsilon is not None:
+            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
+            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+        actions = t.empty((B,) + k.shape, dtype=getattr(t, k.dtype), device=self.device)
+        row = t.empty(B, dtype=t.int32, device=self.device)
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            actions.fill_(k.no_row)
+            row.fill_(-1)
+            return actions, row
+        self.handle.call(k.pick, _lib.ptr(aft.offsets), _lib.ptr(getattr(aft, k.field)), aft.cap, _lib.ptr(v),
+                         max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
+                         _lib.ptr(tag), _lib.ptr(actions), _lib.ptr(row), self._s())
+        self._keep = (v, epsilon, tag)
+        return actions, row
+
     def afterstates(self, dice=None, cap=None, feat=True, obs=False, out=None):
         """The successor positions of each env's roll (narde_afterstates; what
         a TD-Gammon value network scores, README.md:42-102), for dice (B,2) in
@@ -360,40 +430,7 @@ class VecNardeEnv:
         still holds the true counts."""
         if self.full:
             raise ValueError('afterstates() is rules="ref2" only')
-        B, t = self.num_envs, self.torch
-        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
-        if out is not None:
-            offsets = out.offsets
-            cap = out.cap if cap is None else int(cap)
-            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
-                                       ("codes", out.codes, (2,), t.int16), ("feat", out.feat, (198,), t.float32),
-                                       ("obs", out.obs, (24,), t.int32), ("reward", out.reward, (), t.int8)):
-                if a is None:
-                    continue
-                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
-                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
-                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
-                if not ok:
-                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
-        else:
-            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
-            if cap is None:
-                self.handle.call("narde_afterstates", _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None,
-                                 None, self._s())
-                cap = int(offsets[B].item())  # the one synchronise
-            cap = int(cap)
-            if cap < 0:
-                raise ValueError("cap must be >= 0")
-            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
-            out = Afterstates(offsets, mk(True, (), t.int32), mk(True, (2,), t.int16), mk(feat, (198,), t.float32),
-                              mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
-        if cap < 0:
-            raise ValueError("cap must be >= 0")
-        rows = (out.row_env, out.codes, out.feat, out.obs, out.reward)
-        self.handle.call("narde_afterstates", _lib.ptr(d), cap, _lib.ptr(offsets),
-                         *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
-        self._keep = (d,)
-        return out._replace(cap=cap)
+        return self._expand_rows(_REF2_ROWS, dice, cap, feat, obs, out)
 
     def pick_afterstate(self, aft, values, perspective="white", epsilon=None, tag=None, seed=0):
         """Value-greedy play (narde_afterstate_pick): per env the row of `aft`
@@ -406,31 +443,7 @@ class VecNardeEnv:
         row instead.  Call it before the step (it reads who moves).
         Returns (actions (B,2) int16 for step(), row (B,) int32; -1 and
         (0, 0) for an env with no row)."""
-        if perspective not in PERSPECTIVES:
-            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
-        B, t = self.num_envs, self.torch
-        v = values
-        if v.dim() == 2 and v.shape[1] == 1:
-            v = v[:, 0]
-        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
-                or (v.shape[0] > 1 and v.stride(0) < 1)):
-            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
-        if (epsilon is None) != (tag is None):
-            raise ValueError("epsilon and tag go together")
-        if epsilon is not None:
-            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
-            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
-        actions = t.empty((B, 2), dtype=t.int16, device=self.device)
-        row = t.empty(B, dtype=t.int32, device=self.device)
-        if aft.cap == 0:  # no row anywhere (and no array to read)
-            actions.zero_()
-            row.fill_(-1)
-            return actions, row
-        self.handle.call("narde_afterstate_pick", _lib.ptr(aft.offsets), _lib.ptr(aft.codes), aft.cap, _lib.ptr(v),
-                         max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
-                         _lib.ptr(tag), _lib.ptr(actions), _lib.ptr(row), self._s())
-        self._keep = (v, epsilon, tag)
-        return actions, row
+        return self._pick_rows(_REF2_ROWS, aft, values, perspective, epsilon, tag, seed)
 
     def turn_afterstates(self, dice=None, cap=None, feat=True, obs=False, out=None):
         """rules="full4": the distinct positions each env's whole turn can
@@ -450,73 +463,16 @@ class VecNardeEnv:
         capture (its workspace is allocated then)."""
         if not self.full:
             raise ValueError('turn_afterstates() is rules="full4" only')
-        B, t = self.num_envs, self.torch
-        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
-        if out is not None:
-            offsets = out.offsets
-            cap = out.cap if cap is None else int(cap)
-            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
-                                       ("play", out.play, (4, 2), t.int8), ("feat", out.feat, (198,), t.float32),
-                                       ("obs", out.obs, (24,), t.int32), ("reward", out.reward, (), t.int8)):
-                if a is None:
-                    continue
-                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
-                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
-                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
-                if not ok:
-                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
-        else:
-            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
-            if cap is None:
-                self.handle.call("narde_turn_afterstates", _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None,
-                                 None, self._s())
-                cap = int(offsets[B].item())  # the one synchronise
-            cap = int(cap)
-            if cap < 0:
-                raise ValueError("cap must be >= 0")
-            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
-            out = TurnAfterstates(offsets, mk(True, (), t.int32), mk(True, (4, 2), t.int8), mk(feat, (198,), t.float32),
-                                  mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
-        if cap < 0:
-            raise ValueError("cap must be >= 0")
-        rows = (out.row_env, out.play, out.feat, out.obs, out.reward)
-        self.handle.call("narde_turn_afterstates", _lib.ptr(d), cap, _lib.ptr(offsets),
-                         *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
-        self._keep = (d,)
-        return out._replace(cap=cap)
+        return self._expand_rows(_FULL4_ROWS, dice, cap, feat, obs, out)
 
     def pick_turn(self, aft, values, perspective="white", epsilon=None, tag=None, seed=0):
         """pick_afterstate() over turn_afterstates' rows (narde_turn_pick: the
         same perspective, tie, NaN and explore-draw rules).  Returns (play
         (B,4,2) int8 for step(), row (B,) int32; -1 and an all -1 play for
         an env with no row)."""
-        if perspective not in PERSPECTIVES:
-            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
         if not self.full:
             raise ValueError('pick_turn() is rules="full4" only')
-        B, t = self.num_envs, self.torch
-        v = values
-        if v.dim() == 2 and v.shape[1] == 1:
-            v = v[:, 0]
-        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
-                or (v.shape[0] > 1 and v.stride(0) < 1)):
-            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
-        if (epsilon is None) != (tag is None):
-            raise ValueError("epsilon and tag go together")
-        if epsilon is not None:
-            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
-            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
-        play = t.empty((B, 4, 2), dtype=t.int8, device=self.device)
-        row = t.empty(B, dtype=t.int32, device=self.device)
-        if aft.cap == 0:  # no row anywhere (and no array to read)
-            play.fill_(-1)
-            row.fill_(-1)
-            return play, row
-        self.handle.call("narde_turn_pick", _lib.ptr(aft.offsets), _lib.ptr(aft.play), aft.cap, _lib.ptr(v),
-                         max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
-                         _lib.ptr(tag), _lib.ptr(play), _lib.ptr(row), self._s())
-        self._keep = (v, epsilon, tag)
-        return play, row
+        return self._pick_rows(_FULL4_ROWS, aft, values, perspective, epsilon, tag, seed)
 
     def legal_full(self, dice=None):
         """FULL4: (B,) int64 legal words (first sub-move set | max dice << 56)

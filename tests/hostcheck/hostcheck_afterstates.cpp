@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../gym-narde_amd/csrc/narde_rules.h"
+#include "hostcheck_rows.h"
 
 using namespace narde;
 
@@ -31,9 +32,7 @@ int64_t hc_afterstates(int64_t n, const int8_t* board, const uint8_t* off, const
     const int d0 = dice[2 * i], d1 = dice[2 * i + 1];
     plays[i] = 0;
     if (d0 >= 1 && d0 <= 6 && d1 >= 1 && d1 <= 6) {
-      uint4 a, b;
-      record_from_board(board + i * 24, off[2 * i], off[2 * i + 1], ft[2 * i], ft[2 * i + 1], player[i], 0u, 0u, a, b);
-      const Side s = side_from_record(a, b);
+      const Side s = load_side(board + i * 24, off + 2 * i, ft + 2 * i, player[i]);
       Legal l;
       legal2(s, d0, d1, l);
       plays[i] = play_walk(s, d0, d1, kPlayStep, l, [](int, int, int, uint32_t, bool) {});
@@ -53,11 +52,7 @@ int64_t hc_afterstates(int64_t n, const int8_t* board, const uint8_t* off, const
           play_codes(y, c1, c2);
           codes[2 * row] = (int16_t)c1;
           codes[2 * row + 1] = (int16_t)c2;
-          uint4 ra, rb;
-          side_to_record(c, ra, rb);
-          board_from_record(ra, rb, boards + row * 24, offs + 2 * row, nullptr, players + row, nullptr);
-          reward[row] = (int8_t)rew;
-          for (int col = 0; col < 198; ++col) feat[row * 198 + col] = tes_value(ra, rb, col);
+          write_row(c, rew, row, boards, offs, players, reward, feat);
         }
         ++row;
       }
@@ -72,9 +67,7 @@ int64_t hc_afterstates(int64_t n, const int8_t* board, const uint8_t* off, const
 // disagree
 int64_t hc_afterstate_key_pairs(const int8_t* board, const uint8_t* off, const uint8_t* ft, int8_t player,
                                 const uint8_t* dice) {
-  uint4 a, b;
-  record_from_board(board, off[0], off[1], ft[0], ft[1], player, 0u, 0u, a, b);
-  const Side s = side_from_record(a, b);
+  const Side s = load_side(board, off, ft, player);
   Legal l;
   legal2(s, dice[0], dice[1], l);
   std::vector<uint32_t> keys;

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../gym-narde_amd/csrc/narde_rules.h"
+#include "hostcheck_rows.h"
 
 using namespace narde;
 
@@ -23,12 +24,6 @@ struct Node {
   uint32_t path;
   uint64_t key;
 };
-
-Side load_side(const int8_t* board, const uint8_t* off, const uint8_t* ft, int8_t player) {
-  uint4 a, b;
-  record_from_board(board, off[0], off[1], ft[0], ft[1], player, 0u, 0u, a, b);
-  return side_from_record(a, b);
-}
 
 // the rows' nodes (level M, less the lower die's at M = 1 when the higher
 // has one); returns M.  front: the largest level met.
@@ -99,11 +94,7 @@ int64_t hc_turn_afterstates(int64_t n, const int8_t* board, const uint8_t* off, 
           step_end(c, false, term, rew);
           const uint64_t pw = turn_path_play(nd.path, M, dh, dl);
           memcpy(play + row * 8, &pw, 8);
-          uint4 ra, rb;
-          side_to_record(c, ra, rb);
-          board_from_record(ra, rb, boards + row * 24, offs + 2 * row, nullptr, players + row, nullptr);
-          reward[row] = (int8_t)rew;
-          for (int col = 0; col < 198; ++col) feat[row * 198 + col] = tes_value(ra, rb, col);
+          write_row(c, rew, row, boards, offs, players, reward, feat);
         }
         ++row;
       }

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-np_ = lambda t: t.cpu().numpy()  # noqa: E731
+from afterstate_checks import _check_pick, _env, _equal, _pick_ref, _scored_ply, np_  # noqa: E402
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -51,25 +51,6 @@ def _first(case, B):
     return _take(case, big[:B] if B <= 3 else list(range(B - 3)) + big)
 
 
-def _env(st, seed=3, autoreset=False, **kw):
-    from gym_narde.vector import VecNardeEnv
-
-    env = VecNardeEnv(st[0].shape[0], device="cuda:0", seed=seed, autoreset=autoreset, **kw)
-    env.set_state(st[0], st[1], st[2], st[3])
-    return env
-
-
-def _equal(aft, want, rows=None):
-    n = int(want["offsets"][-1]) if rows is None else rows
-    assert np.array_equal(np_(aft.offsets), want["offsets"])
-    assert np.array_equal(np_(aft.row_env)[:n], want["row_env"][:n])
-    assert np.array_equal(np_(aft.codes)[:n], want["codes"][:n])
-    assert np.array_equal(np_(aft.reward)[:n], want["reward"][:n])
-    assert np.array_equal(np_(aft.feat)[:n].view(np.uint32), want["feat"][:n].view(np.uint32))
-    if aft.obs is not None:
-        assert np.array_equal(np_(aft.obs)[:n], want["obs"][:n].astype(np.int32))
-
-
 @pytest.mark.parametrize("B", [1, 65, 1003, 4004])
 def test_rows_equal_the_restatement(case, B):
     """B = 1, one wave plus one lane, 1,003 and the whole case: every output,
@@ -99,34 +80,6 @@ def test_offsets_carry_across_scan_tiles(case):
     assert np.array_equal(np_(aft.codes), np.tile(want["codes"], (rep, 1)))
     assert np.array_equal(np_(aft.row_env), np.repeat(np.arange(cnt.size), cnt).astype(np.int32))
     env.close()
-
-
-def _pick_ref(offsets, cap, values, black, perspective):
-    """torch.max / torch.min over each env's rows (below cap): (row, NaN as
-    torch takes it, the first of equal values)."""
-    v = torch.as_tensor(values)
-    rows = np.full(len(offsets) - 1, -1, np.int32)
-    for e in range(len(offsets) - 1):
-        r0, r1 = int(offsets[e]), min(int(offsets[e + 1]), cap)
-        if r1 <= r0:
-            continue
-        seg = v[r0:r1]
-        smallest = perspective == "white" and black[e]
-        # first extremum: torch.min / max(dim) on the CPU return it
-        k = int((torch.min(seg, 0) if smallest else torch.max(seg, 0)).indices)
-        ext = seg[k]
-        same = torch.isnan(seg) if torch.isnan(ext) else seg == ext
-        rows[e] = r0 + int(torch.nonzero(same)[0])
-    return rows
-
-
-def _check_pick(env, aft, values, black, perspective, codes):
-    actions, row = env.pick_afterstate(aft, values, perspective=perspective)
-    want = _pick_ref(np_(aft.offsets), aft.cap, np_(values), black, perspective)
-    assert np.array_equal(np_(row), want)
-    want_act = np.where((want >= 0)[:, None], codes[np.maximum(want, 0)], 0)
-    assert np.array_equal(np_(actions), want_act)
-    return want
 
 
 def test_cap_cuts_rows_not_offsets(case):
@@ -250,14 +203,6 @@ def test_pick_explores_uniformly_over_the_rows(case):
     env.close()
 
 
-def _scored_ply(env, out, w):
-    aft = env.afterstates(out=out)
-    values = (aft.feat * w).sum(1)
-    actions, row = env.pick_afterstate(aft, values, perspective="white")
-    env.step(actions)
-    return actions, row
-
-
 def test_graph_capture_equals_eager():
     """afterstates(cap) + pick + step captured once (linear) and replayed: no
     allocation or synchronise inside the call."""
@@ -267,6 +212,7 @@ def test_graph_capture_equals_eager():
     envs = [VecNardeEnv(B, device="cuda:0", seed=seed) for _ in range(2)]
     dev = envs[0].device
     w = torch.linspace(-1, 1, 198, device=dev)
+    score = lambda feat: (feat * w).sum(1)  # noqa: E731
     mk = lambda: Afterstates(torch.zeros(B + 1, dtype=torch.int32, device=dev),  # noqa: E731
                              torch.zeros(cap, dtype=torch.int32, device=dev),
                              torch.zeros((cap, 2), dtype=torch.int16, device=dev),
@@ -281,13 +227,13 @@ def test_graph_capture_equals_eager():
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         with torch.cuda.graph(graph, stream=side):
-            g_actions, g_row = _scored_ply(envs[0], outs[0], w)
+            g_actions, g_row = _scored_ply(envs[0], outs[0], score)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     for _ in range(3):
         graph.replay()
         torch.cuda.synchronize()
-        e_actions, e_row = _scored_ply(envs[1], outs[1], w)
+        e_actions, e_row = _scored_ply(envs[1], outs[1], score)
         torch.cuda.synchronize()
         assert int(outs[1].offsets[B]) <= cap
         assert torch.equal(g_actions, e_actions) and torch.equal(g_row, e_row)

@@ -9,13 +9,13 @@ import pytest
 
 import oracle as O
 import turn_afterstates_ref as R
-from test_gpu_afterstates import _pick_ref
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-np_ = lambda t: t.cpu().numpy()  # noqa: E731
+from afterstate_checks import _check_pick, _equal, _pick_ref, _scored_ply, np_  # noqa: E402
+from afterstate_checks import _env as _env_of  # noqa: E402
 B = 1003
 BIG_AT = (0, 500, B - 1)  # the 2,065-row position: first env, mid-wave among light envs, last env
 KEYS = ("board", "off", "ft", "player", "dice")
@@ -51,23 +51,8 @@ def case():
     return st, ref
 
 
-def _env(st, seed=3, autoreset=False):
-    from gym_narde.vector import VecNardeEnv
-
-    env = VecNardeEnv(len(st["player"]), device="cuda:0", seed=seed, autoreset=autoreset, rules="full4")
-    env.set_state(st["board"], st["off"], st["ft"], st["player"])
-    return env
-
-
-def _equal(aft, want, rows=None):
-    n = int(want["offsets"][-1]) if rows is None else rows
-    assert np.array_equal(np_(aft.offsets), want["offsets"])
-    assert np.array_equal(np_(aft.row_env)[:n], want["row_env"][:n])
-    assert np.array_equal(np_(aft.play)[:n], want["play"][:n])
-    assert np.array_equal(np_(aft.reward)[:n], want["reward"][:n])
-    assert np.array_equal(np_(aft.feat)[:n].view(np.uint32), want["feat"][:n].view(np.uint32))
-    if aft.obs is not None:
-        assert np.array_equal(np_(aft.obs)[:n], want["obs"][:n])
+def _env(st):
+    return _env_of([st[k] for k in KEYS], rules="full4")
 
 
 def test_rows_equal_the_enumerator(case):
@@ -75,7 +60,7 @@ def test_rows_equal_the_enumerator(case):
     env = _env(st)
     aft = env.turn_afterstates(dice=st["dice"], obs=True)
     assert aft.cap == int(want["offsets"][-1]) and aft.feat.shape == (aft.cap, 198)
-    _equal(aft, want)
+    _equal(aft, want, action="play")
     # feat=False / obs=False leave those arrays out, the rest unchanged
     lean = env.turn_afterstates(dice=st["dice"], feat=False)
     assert lean.feat is None and lean.obs is None
@@ -115,7 +100,7 @@ def test_cap_cuts_rows_not_offsets_and_count_only(case):
                           torch.full((total,), -7, dtype=torch.int8, device=dev), cap)
     aft = env.turn_afterstates(dice=st["dice"], out=out)
     assert aft.cap == cap
-    _equal(aft, want, rows=cap)  # offsets: the true counts
+    _equal(aft, want, rows=cap, action="play")  # offsets: the true counts
     assert int(np_(aft.offsets)[-1]) == total > cap
     for a in (aft.row_env, aft.play, aft.feat, aft.obs, aft.reward):
         assert (np_(a)[cap:] == -7).all()
@@ -144,7 +129,7 @@ def test_device_dice_equal_given_dice():
         assert torch.equal(x, y)
     s = env.get_state()
     want = R.enumerate_turns(np_(s["board"]), np_(s["off"]), np_(s["first_turn"]), np_(s["player"]), np_(env.dice()))
-    _equal(a, want)
+    _equal(a, want, action="play")
     env.close()
 
 
@@ -155,15 +140,6 @@ def test_ref2_is_refused():
     with pytest.raises(ValueError):
         env.turn_afterstates()
     env.close()
-
-
-def _check_pick(env, aft, values, black, perspective, plays, **kw):
-    play, row = env.pick_turn(aft, values, perspective=perspective, **kw)
-    want = _pick_ref(np_(aft.offsets), aft.cap, np_(values), black, perspective)
-    assert np.array_equal(np_(row), want)
-    want_play = np.where((want >= 0)[:, None, None], plays[np.maximum(want, 0)], -1)
-    assert np.array_equal(np_(play), want_play)
-    return want
 
 
 @pytest.mark.parametrize("perspective", ["white", "mover"])
@@ -247,15 +223,6 @@ def test_step_carries_out_the_picked_play(case):
     env.close()
 
 
-def _scored_ply(env, out, net):
-    aft = env.turn_afterstates(out=out)
-    with torch.no_grad():
-        values = net(aft.feat).reshape(-1)
-    play, row = env.pick_turn(aft, values, perspective="white")
-    env.step(play)
-    return play, row
-
-
 def test_graph_capture_equals_eager():
     """turn_afterstates(cap) + a small MLP + pick_turn + step captured once and
     replayed five times: no allocation or synchronise inside the calls."""
@@ -266,6 +233,7 @@ def test_graph_capture_equals_eager():
     dev = envs[0].device
     torch.manual_seed(0)
     net = torch.nn.Sequential(torch.nn.Linear(198, 16), torch.nn.Sigmoid(), torch.nn.Linear(16, 1)).to(dev)
+    score = lambda feat: net(feat).reshape(-1)  # noqa: E731
     mk = lambda: TurnAfterstates(torch.zeros(n + 1, dtype=torch.int32, device=dev),  # noqa: E731
                                  torch.zeros(cap, dtype=torch.int32, device=dev),
                                  torch.zeros((cap, 4, 2), dtype=torch.int8, device=dev),
@@ -284,13 +252,13 @@ def test_graph_capture_equals_eager():
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.stream(side):
         with torch.cuda.graph(graph, stream=side):
-            g_play, g_row = _scored_ply(envs[0], outs[0], net)
+            g_play, g_row = _scored_ply(envs[0], outs[0], score)
     torch.cuda.current_stream().wait_stream(side)
     torch.cuda.synchronize()
     for _ in range(5):
         graph.replay()
         torch.cuda.synchronize()
-        e_play, e_row = _scored_ply(envs[1], outs[1], net)
+        e_play, e_row = _scored_ply(envs[1], outs[1], score)
         torch.cuda.synchronize()
         assert 0 < int(outs[1].offsets[n]) <= cap
         assert torch.equal(g_play, e_play) and torch.equal(g_row, e_row)

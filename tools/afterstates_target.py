@@ -4,7 +4,7 @@ M.25): seed 0, 40 plies of random self-play, device dice, cap from a count
 pass.
 
   launches  warm-up, then --reps launches each of afterstates (k_aft_count +
-            k_aft_scan + k_aft_fill), pick_afterstate (k_aft_pick) and
+            k_aft_scan + k_aft_fill), pick_afterstate (k_aft_pick<unsigned int>) and
             tesauro198 (k_tesauro198_rows) on the same env.  Run it under
             `rocprofv3 --kernel-trace --stats` for the kernels' durations; it
             writes the row count and the algorithmic bytes to --json.
@@ -18,7 +18,7 @@ pass.
 --rules full4 (MEASUREMENT_LOG M.26): the same on a
 rules="full4" env -- turn_afterstates (k_turn_count + k_turn_overflow<count>
 + k_aft_scan + k_turn_fill + k_turn_overflow<fill>) and pick_turn
-(k_turn_pick) --, with REF2's afterstates launched on a REF2 env in the same
+(k_aft_pick<unsigned long>) --, with REF2's afterstates launched on a REF2 env in the same
 trace, and the share of envs that take the overflow path (a level of more
 than 256 nodes: counted on the CPU by the test-only host build of the same
 rule functions, tests/hostcheck, on the env's states and dice).
@@ -38,9 +38,11 @@ sys.path.insert(0, os.path.join(ROOT, "gym-narde_amd"))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
 
 HBM_PEAK = 8.0e12
-KERNELS = ("k_aft_count", "k_aft_scan", "k_aft_fill", "k_aft_pick", "k_tesauro198_rows")
+# (k_aft_pick is one template: <unsigned int, 0> picks REF2's code pairs,
+# <unsigned long, ~0> FULL4's plays)
+KERNELS = ("k_aft_count", "k_aft_scan", "k_aft_fill", "k_aft_pick<unsigned int", "k_tesauro198_rows")
 KERNELS_FULL4 = ("k_turn_count", "k_turn_overflow<false", "k_aft_scan", "k_turn_fill", "k_turn_overflow<true",
-                 "k_turn_pick", "k_aft_count", "k_aft_fill", "k_tesauro198_rows")
+                 "k_aft_pick<unsigned long", "k_aft_count", "k_aft_fill", "k_tesauro198_rows")
 FAST_FRONT = 256  # kernels_turn_afterstates.h kTurnFront
 
 
