@@ -34,35 +34,14 @@
 #include <stdint.h>
 
 #include "../../include/narde.h"
+#include "host_common.h"
 #include "narde_rules.h"
 
-namespace narde_abi {
-int set_error(int code, const char* what);  // narde.hip: narde_last_error()'s buffer
-}
+using namespace narde_host;
 
 namespace {
 
 constexpr int kLearnThreads = 1024;
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != d) (void)hipSetDevice(d);
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-int check_launch(const char* what) {
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return narde_abi::set_error(NARDE_EHIP, hipGetErrorString(e));
-  (void)what;
-  return NARDE_OK;
-}
-
-int bad(const char* what) { return narde_abi::set_error(NARDE_EINVAL, what); }
 
 // block-wide max / sum over kLearnThreads threads (wave shuffles, then the
 // 16 wave results through LDS); every thread gets the result
@@ -1114,30 +1093,29 @@ extern "C" {
 int narde_per_sample(int device, const float* p, const float* cdf, int64_t n, int64_t batch, uint64_t seed,
                      int64_t* counter, double* beta, double beta_inc, int64_t* idx, float* w, float* u,
                      uint32_t* scratch, void* stream) {
-  if (!p || !cdf || !counter || !beta || !idx || !w) return bad("NULL argument");
-  if (n <= 0 || batch <= 0 || batch > (int64_t(1) << 24)) return bad("need n > 0 and 0 < batch <= 2^24");
+  if (!p || !cdf || !counter || !beta || !idx || !w) return fail(NARDE_EINVAL, "NULL argument");
+  if (n <= 0 || batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "need n > 0 and 0 < batch <= 2^24");
   DeviceGuard dg(device);
   const unsigned blocks = (unsigned)((batch + kSampleWaves - 1) / kSampleWaves);
   k_per_sample<<<blocks, 64 * kSampleWaves, 0, (hipStream_t)stream>>>(p, cdf, n, (int)batch, (uint32_t)seed,
                                                                       (uint32_t)(seed >> 32), counter, beta, idx, w, u);
-  const int rc = check_launch("k_per_sample");
-  if (rc != NARDE_OK) return rc;
+  if (const int rc = check_launch("k_per_sample")) return rc;
   k_per_finish<<<1, 1024, 0, (hipStream_t)stream>>>((int)batch, counter, beta, beta_inc, w);
   return check_launch("k_per_finish");
 }
 
 int narde_per_prefix(int device, const float* prio, int64_t n, double alpha, float* p, float* cdf, float* chunk,
                      int64_t chunks, void* stream) {
-  if (!prio || !p || !cdf || !chunk) return bad("NULL argument");
-  if (n <= 0 || n > (int64_t(1) << 31) - kScanChunk) return bad("need 0 < n < 2^31 - 1024");
-  if ((((uintptr_t)prio | (uintptr_t)p | (uintptr_t)cdf) & 15u) != 0u) return bad("prio, p and cdf must be 16-byte aligned");
+  if (!prio || !p || !cdf || !chunk) return fail(NARDE_EINVAL, "NULL argument");
+  if (n <= 0 || n > (int64_t(1) << 31) - kScanChunk) return fail(NARDE_EINVAL, "need 0 < n < 2^31 - 1024");
+  if (!aligned16(prio) || !aligned16(p) || !aligned16(cdf))
+    return fail(NARDE_EINVAL, "prio, p and cdf must be 16-byte aligned");
   const int64_t blocks64 = (n + kScanChunk - 1) / kScanChunk;
-  if (chunks < blocks64) return bad("chunk holds fewer totals than n needs");
+  if (chunks < blocks64) return fail(NARDE_EINVAL, "chunk holds fewer totals than n needs");
   DeviceGuard dg(device);
   const unsigned blocks = (unsigned)blocks64;
   k_per_chunk_sums<<<blocks, kScanThreads, 0, (hipStream_t)stream>>>(prio, n, (float)alpha, chunk);
-  const int rc = check_launch("k_per_chunk_sums");
-  if (rc != NARDE_OK) return rc;
+  if (const int rc = check_launch("k_per_chunk_sums")) return rc;
   k_per_scan<<<blocks, kScanThreads, 0, (hipStream_t)stream>>>(prio, n, (float)alpha, chunk, p, cdf);
   return check_launch("k_per_scan");
 }
@@ -1146,9 +1124,9 @@ int narde_gather_batch(int device, const int64_t* idx, int64_t batch, int state_
                        int64_t next_stride, int64_t capacity, const int64_t* action, const float* reward,
                        const float* done, float* s, float* ns, int64_t* a, float* r, float* d, void* stream) {
   if (!idx || !obs || !action || !reward || !done || !s || !ns || !a || !r || !d)
-    return bad("NULL argument");
-  if (batch <= 0 || state_size <= 0 || batch * state_size >= (int64_t(1) << 31)) return bad("bad sizes");
-  if (capacity <= 0 || next_stride < 0 || next_stride >= capacity) return bad("bad ring geometry");
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (batch <= 0 || state_size <= 0 || batch * state_size >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "bad sizes");
+  if (capacity <= 0 || next_stride < 0 || next_stride >= capacity) return fail(NARDE_EINVAL, "bad ring geometry");
   DeviceGuard dg(device);
   const int64_t total = batch * state_size;
   k_gather_batch<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(
@@ -1158,8 +1136,8 @@ int narde_gather_batch(int device, const int64_t* idx, int64_t batch, int state_
 
 int narde_rowmax_addend(int device, const float* base, int64_t ld, const float* tab, int64_t ld_tab,
                         const int64_t* rows, int64_t n, float* out, void* stream) {
-  if (!base || !tab || !rows || !out) return bad("NULL argument");
-  if (n < 0 || n > (int64_t(1) << 31) - 4 || ld < 576 || ld_tab < 576) return bad("bad sizes");
+  if (!base || !tab || !rows || !out) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 0 || n > (int64_t(1) << 31) - 4 || ld < 576 || ld_tab < 576) return fail(NARDE_EINVAL, "bad sizes");
   if (n == 0) return NARDE_OK;
   DeviceGuard dg(device);
   k_rowmax_addend<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(base, ld, tab, ld_tab, rows, (int)n,
@@ -1167,15 +1145,15 @@ int narde_rowmax_addend(int device, const float* base, int64_t ld, const float* 
   return check_launch("k_rowmax_addend");
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0u; }
-
 int narde_dqn_heads_forward(int device, const float* f, int64_t ldf, const float* w1, int64_t ldw1,
                             const float* b1, const float* w2, int64_t ldw2, const float* b2, const int64_t* a,
                             int64_t n, float* q1, float* q2, void* stream) {
-  if (!f || !w1 || !b1 || !w2 || !b2 || !a || !q1 || !q2) return bad("NULL argument");
-  if (n < 0 || n > (int64_t(1) << 31) - 4) return bad("bad batch");
-  if (ldf < kHeadF || ldw1 < kHeadF || ldw2 < kW2 || (ldf | ldw1 | ldw2) & 3) return bad("bad leading dimensions");
-  if (!aligned16(f) || !aligned16(w1) || !aligned16(w2)) return bad("f / w1 / w2 must be 16-byte aligned");
+  if (!f || !w1 || !b1 || !w2 || !b2 || !a || !q1 || !q2) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 0 || n > (int64_t(1) << 31) - 4) return fail(NARDE_EINVAL, "bad batch");
+  if (ldf < kHeadF || ldw1 < kHeadF || ldw2 < kW2 || (ldf | ldw1 | ldw2) & 3)
+    return fail(NARDE_EINVAL, "bad leading dimensions");
+  if (!aligned16(f) || !aligned16(w1) || !aligned16(w2))
+    return fail(NARDE_EINVAL, "f / w1 / w2 must be 16-byte aligned");
   if (n == 0) return NARDE_OK;
   DeviceGuard dg(device);
   k_heads_gather<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(f, ldf, w1, ldw1, b1, w2, ldw2, b2, a,
@@ -1186,34 +1164,34 @@ int narde_dqn_heads_forward(int device, const float* f, int64_t ldf, const float
 int narde_dqn_heads_backward(int device, const float* g1, const float* g2, const float* f, int64_t ldf,
                              const float* w1, int64_t ldw1, const float* w2, int64_t ldw2, const int64_t* a,
                              int64_t n, float* gf, float* gw1, float* gb1, float* gw2, float* gb2, void* stream) {
-  if (!g1 || !g2 || !f || !w1 || !w2 || !a || !gf || !gw1 || !gb1 || !gw2 || !gb2) return bad("NULL argument");
-  if (n < 0 || n > (int64_t(1) << 31) - 4) return bad("bad batch");
-  if (ldf < kHeadF || ldw1 < kHeadF || ldw2 < kW2 || (ldw1 | ldw2) & 3) return bad("bad leading dimensions");
-  if (!aligned16(w1) || !aligned16(w2) || !aligned16(gf)) return bad("w1 / w2 / gf must be 16-byte aligned");
+  if (!g1 || !g2 || !f || !w1 || !w2 || !a || !gf || !gw1 || !gb1 || !gw2 || !gb2)
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 0 || n > (int64_t(1) << 31) - 4) return fail(NARDE_EINVAL, "bad batch");
+  if (ldf < kHeadF || ldw1 < kHeadF || ldw2 < kW2 || (ldw1 | ldw2) & 3)
+    return fail(NARDE_EINVAL, "bad leading dimensions");
+  if (!aligned16(w1) || !aligned16(w2) || !aligned16(gf))
+    return fail(NARDE_EINVAL, "w1 / w2 / gf must be 16-byte aligned");
   DeviceGuard dg(device);
   if (n > 0) {
     k_heads_grad_f<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(g1, g2, w1, ldw1, w2, ldw2, a, (int)n,
                                                                              gf);
-    const int rc = check_launch("k_heads_grad_f");
-    if (rc != NARDE_OK) return rc;
+    if (const int rc = check_launch("k_heads_grad_f")) return rc;
   }
   k_heads_grad_w<<<2 * kCodes, kGwThreads, 0, (hipStream_t)stream>>>(g1, g2, f, ldf, a, (int)n, gw1, gb1, gw2, gb2);
   return check_launch("k_heads_grad_w");
 }
 
-
 int narde_relu_bias_grad(int device, const float* gh, const float* h, int64_t n, int64_t cols, float* g,
                          float* db, float* scratch, void* stream) {
-  if (!gh || !h || !g || !db || !scratch) return bad("NULL argument");
-  if (n <= 0 || cols <= 0 || cols > 4096 || n * cols >= (int64_t(1) << 31)) return bad("bad sizes");
+  if (!gh || !h || !g || !db || !scratch) return fail(NARDE_EINVAL, "NULL argument");
+  if (n <= 0 || cols <= 0 || cols > 4096 || n * cols >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "bad sizes");
   DeviceGuard dg(device);
   const int slices = (int)((n + kRbRows - 1) / kRbRows);
   // scratch: slices x cols partial sums
   const unsigned groups = (unsigned)((cols + 63) / 64);
   k_relu_grad_partial<<<dim3(groups, (unsigned)slices), 256, 0, (hipStream_t)stream>>>(gh, h, (int)n, (int)cols, g,
                                                                                      scratch);
-  const int rc = check_launch("k_relu_grad_partial");
-  if (rc != NARDE_OK) return rc;
+  if (const int rc = check_launch("k_relu_grad_partial")) return rc;
   k_bias_grad_sum<<<groups, 256, 0, (hipStream_t)stream>>>(scratch, slices, (int)cols, db);
   return check_launch("k_bias_grad_sum");
 }
@@ -1221,8 +1199,9 @@ int narde_relu_bias_grad(int device, const float* gh, const float* h, int64_t n,
 int narde_dqn_loss(int device, const float* q1, const float* q2, const float* m1, const float* m2, const float* r,
                    const float* d, const float* w, int64_t batch, float gamma, float* td, float* loss,
                    float* loss_copy, float* g1, float* g2, void* stream) {
-  if (!q1 || !q2 || !m1 || !m2 || !r || !d || !w || !td || !loss || !g1 || !g2) return bad("NULL argument");
-  if (batch <= 0 || batch > (int64_t(1) << 24)) return bad("bad batch");
+  if (!q1 || !q2 || !m1 || !m2 || !r || !d || !w || !td || !loss || !g1 || !g2)
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "bad batch");
   DeviceGuard dg(device);
   k_dqn_loss<<<1, kLearnThreads, 0, (hipStream_t)stream>>>(q1, q2, m1, m2, r, d, w, (int)batch, gamma, td, loss,
                                                            loss_copy, g1, g2);
@@ -1232,9 +1211,9 @@ int narde_dqn_loss(int device, const float* q1, const float* q2, const float* m1
 int narde_prio_update(int device, const int64_t* idx, const float* td, int64_t batch, float eps, float* prio,
                       float* max_prio, float* epsilon, float eps_min, float eps_decay, int64_t* cursor,
                       int64_t cursor_add, int64_t cursor_mod, int64_t* tag, void* stream) {
-  if (!idx || !td || !prio || !max_prio) return bad("NULL argument");
-  if (batch <= 0 || batch > (int64_t(1) << 24)) return bad("bad batch");
-  if (cursor && (cursor_mod <= 0 || cursor_add < 0)) return bad("bad cursor step");
+  if (!idx || !td || !prio || !max_prio) return fail(NARDE_EINVAL, "NULL argument");
+  if (batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "bad batch");
+  if (cursor && (cursor_mod <= 0 || cursor_add < 0)) return fail(NARDE_EINVAL, "bad cursor step");
   DeviceGuard dg(device);
   k_prio_update<<<1, kLearnThreads, 0, (hipStream_t)stream>>>(idx, td, (int)batch, eps, prio, max_prio, epsilon,
                                                               eps_min, eps_decay, cursor, cursor_add, cursor_mod,
@@ -1242,17 +1221,16 @@ int narde_prio_update(int device, const int64_t* idx, const float* td, int64_t b
   return check_launch("k_prio_update");
 }
 
-
 int narde_adam_clip(int device, int n_tensors, float* const* params, const float* const* grads, float* const* m,
                     float* const* v, const int64_t* sizes, int64_t* step, float lr, float beta1, float beta2,
                     float eps, float max_norm, float* scratch, void* stream) {
-  if (n_tensors <= 0 || n_tensors > kMaxTensors) return bad("1..8 tensors");
-  if (!params || !grads || !m || !v || !sizes || !step || !scratch) return bad("NULL argument");
+  if (n_tensors <= 0 || n_tensors > kMaxTensors) return fail(NARDE_EINVAL, "1..8 tensors");
+  if (!params || !grads || !m || !v || !sizes || !step || !scratch) return fail(NARDE_EINVAL, "NULL argument");
   ParamTable t{};
   t.count = n_tensors;
   t.off[0] = 0;
   for (int k = 0; k < n_tensors; ++k) {
-    if (!params[k] || !grads[k] || !m[k] || !v[k] || sizes[k] <= 0) return bad("bad tensor");
+    if (!params[k] || !grads[k] || !m[k] || !v[k] || sizes[k] <= 0) return fail(NARDE_EINVAL, "bad tensor");
     t.p[k] = params[k];
     t.g[k] = grads[k];
     t.m[k] = m[k];
@@ -1261,7 +1239,7 @@ int narde_adam_clip(int device, int n_tensors, float* const* params, const float
   }
   for (int k = n_tensors; k < kMaxTensors; ++k) t.off[k + 1] = t.off[n_tensors];
   const int64_t total = t.off[n_tensors];
-  if (total >= (int64_t(1) << 31)) return bad("too many parameters");
+  if (total >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "too many parameters");
   // scratch: kNormBlocks partial sums (the words after them are unused)
   float* partial = scratch;
   DeviceGuard dg(device);
@@ -1273,8 +1251,7 @@ int narde_adam_clip(int device, int n_tensors, float* const* params, const float
     int nb4 = (int)((total4 + 255) / 256);
     nb4 = nb4 < kNormBlocks ? nb4 : kNormBlocks;
     k_grad_sqnorm4<<<nb4, 256, 0, (hipStream_t)stream>>>(t, partial, step);
-    const int rc = check_launch("k_grad_sqnorm4");
-    if (rc != NARDE_OK) return rc;
+    if (const int rc = check_launch("k_grad_sqnorm4")) return rc;
     k_adam4<<<(unsigned)((total4 + 255) / 256), 256, 0, (hipStream_t)stream>>>(t, partial, nb4, max_norm, step, lr,
                                                                               beta1, beta2, eps);
     return check_launch("k_adam4");
@@ -1282,8 +1259,7 @@ int narde_adam_clip(int device, int n_tensors, float* const* params, const float
   int nb = (int)((total + 256 * 16 - 1) / (256 * 16));  // ~16 elements per thread
   nb = nb < kNormBlocks ? nb : kNormBlocks;
   k_grad_sqnorm<<<nb, 256, 0, (hipStream_t)stream>>>(t, partial, step);
-  const int rc = check_launch("k_grad_sqnorm");
-  if (rc != NARDE_OK) return rc;
+  if (const int rc = check_launch("k_grad_sqnorm")) return rc;
   k_adam<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(t, partial, nb, max_norm, step, lr, beta1,
                                                                            beta2, eps);
   return check_launch("k_adam");
@@ -1296,10 +1272,11 @@ int narde_per_sample_gather(int device, const float* p, const float* cdf, int64_
                             float* d, void* stream) {
   if (!p || !cdf || !counter || !beta || !idx || !w || !obs || !action || !reward || !done || !s || !ns || !a || !r ||
       !d)
-    return bad("NULL argument");
-  if (n <= 0 || batch <= 0 || batch > (int64_t(1) << 24)) return bad("need n > 0 and 0 < batch <= 2^24");
-  if (state_size <= 0 || batch * state_size >= (int64_t(1) << 31)) return bad("bad sizes");
-  if (capacity <= 0 || n > capacity || next_stride < 0 || next_stride >= capacity) return bad("bad ring geometry");
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (n <= 0 || batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "need n > 0 and 0 < batch <= 2^24");
+  if (state_size <= 0 || batch * state_size >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "bad sizes");
+  if (capacity <= 0 || n > capacity || next_stride < 0 || next_stride >= capacity)
+    return fail(NARDE_EINVAL, "bad ring geometry");
   DeviceGuard dg(device);
   const unsigned blocks = (unsigned)((batch + kSampleWaves - 1) / kSampleWaves);
   k_per_sample_gather<<<blocks, 64 * kSampleWaves, 0, (hipStream_t)stream>>>(
@@ -1310,8 +1287,9 @@ int narde_per_sample_gather(int device, const float* p, const float* cdf, int64_
 
 int narde_target_max2(int device, const float* nq1, int64_t ld1, const float* base, int64_t ld, const float* tab,
                       int64_t ld_tab, int64_t n, float* m1, int64_t* am1, float* m2, void* stream) {
-  if (!nq1 || !base || !tab || !m1 || !m2) return bad("NULL argument");
-  if (n < 0 || n > (int64_t(1) << 31) - 4 || ld1 < 576 || ld < 576 || ld_tab < 576) return bad("bad sizes");
+  if (!nq1 || !base || !tab || !m1 || !m2) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 0 || n > (int64_t(1) << 31) - 4 || ld1 < 576 || ld < 576 || ld_tab < 576)
+    return fail(NARDE_EINVAL, "bad sizes");
   if (n == 0) return NARDE_OK;
   DeviceGuard dg(device);
   k_target_max2<<<(unsigned)((n + 3) / 4), 256, 0, (hipStream_t)stream>>>(nq1, ld1, base, ld, tab, ld_tab, (int)n,
@@ -1327,9 +1305,9 @@ int narde_dqn_loss_prio(int device, const float* q1, const float* q2, const floa
                         double beta_inc, void* stream) {
   if (!q1 || !q2 || !m1 || !m2 || !r || !d || !w || !td || !loss || !g1 || !g2 || !idx || !prio || !max_prio ||
       !counter || !beta)
-    return bad("NULL argument");
-  if (batch <= 0 || batch > (int64_t(1) << 24)) return bad("bad batch");
-  if (cursor && (cursor_mod <= 0 || cursor_add < 0)) return bad("bad cursor step");
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "bad batch");
+  if (cursor && (cursor_mod <= 0 || cursor_add < 0)) return fail(NARDE_EINVAL, "bad cursor step");
   DeviceGuard dg(device);
   k_dqn_loss_prio<<<1, kLearnThreads, 0, (hipStream_t)stream>>>(q1, q2, m1, m2, r, d, w, (int)batch, gamma, td, loss,
                                                                 loss_copy, g1, g2, idx, eps, prio, max_prio, epsilon,

@@ -500,7 +500,8 @@ __device__ __forceinline__ void pc_put(PcLds& L, int slot, int k, int le, const 
 
 // obs quad qq (points 4qq .. 4qq + 3) of workgroup-local env le from the ply
 // results in LDS: only the two words it needs -- own word wi is dword wi of
-// nib0, opponent word wi is dword 3 of nib0 or wi - 1 of nib1
+// nib0, opponent word wi is dword 3 of nib0 or wi - 1 of nib1.  Both rings:
+// PcLds by (slot, k, le), PpLds by (pair, ring slot, env of the pair)
 template <class Lds>
 __device__ __forceinline__ int4 pc_obs_quad(const Lds& L, int slot, int k, int le, int qq) {
   const int wi = qq >> 1, sh = (qq & 1) * 16;
@@ -778,21 +779,6 @@ __device__ __forceinline__ uint32_t pp_wait(const uint32_t* c, F ok) {
   return v;
 }
 
-// obs quad qq of env el of pair cw, ring slot sl (pc_obs_quad's layout)
-__device__ __forceinline__ int4 pp_obs_quad(const PpLds& L, int cw, int sl, int el, int qq) {
-  const int wi = qq >> 1, sh = (qq & 1) * 16;
-  const uint32_t* n0w = reinterpret_cast<const uint32_t*>(&L.nib0[cw][sl][el]);
-  const uint32_t* n1w = reinterpret_cast<const uint32_t*>(&L.nib1[cw][sl][el]);
-  const uint32_t own = n0w[wi];
-  const uint32_t opp = wi == 0 ? n0w[3] : n1w[wi - 1];
-  int4 v;
-  v.x = nib_at(own, sh) - nib_at(opp, sh);
-  v.y = nib_at(own, sh + 4) - nib_at(opp, sh + 4);
-  v.z = nib_at(own, sh + 8) - nib_at(opp, sh + 8);
-  v.w = nib_at(own, sh + 12) - nib_at(opp, sh + 12);
-  return v;
-}
-
 // consumer: ply p's outputs of pair cw's 64 envs from ring slot sl
 // (pc_emit_ply's store form)
 __device__ __forceinline__ void pp_emit_ply(const PpLds& L, int cw, int sl, int p, int n, int g0, int lane,
@@ -805,7 +791,7 @@ __device__ __forceinline__ void pp_emit_ply(const PpLds& L, int cw, int sl, int 
     for (int q = 0; q < 6; ++q) {
       const int j = lane + 64 * q;
       const int el = j / 6, qq = j - 6 * el;
-      pc_st16(r, (uint32_t)j * 16u, pp_obs_quad(L, cw, sl, el, qq));
+      pc_st16(r, (uint32_t)j * 16u, pc_obs_quad(L, cw, sl, el, qq));
     }
   }
   const uint32_t c = L.rtt[cw][sl][lane];

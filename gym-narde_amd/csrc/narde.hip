@@ -24,41 +24,23 @@
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
 //                       (k_turn_count, k_turn_fill, k_turn_overflow)
 // This file keeps the handle, the host-side checks and every C entry point.
-// The DQN learner kernels are a second translation unit (dqn_learner.hip).
+// The DQN learner kernels are a second translation unit (dqn_learner.hip);
+// host_common.h: the host helpers the two share.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <type_traits>
 
 #include "../../include/narde.h"
+#include "host_common.h"
 #include "narde_rules.h"
 
 using namespace narde;
+using namespace narde_host;
 
-namespace {
-
-constexpr int64_t kHostCap = 4096;
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof g_err, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define HIP_TRY(expr)                                                                   \
-  do {                                                                                  \
-    hipError_t e_ = (expr);                                                             \
-    if (e_ != hipSuccess) return fail(NARDE_EHIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
-
-}  // namespace
+thread_local char narde_host::g_err[512] = "";
 
 #include "device_common.h"
 #include "kernels_state.h"
@@ -72,6 +54,18 @@ int fail(int code, const char* fmt, ...) {
 namespace {
 
 inline int grid(int64_t n) { return (int)((n + kBlock - 1) / kBlock); }
+
+// The narde_host_* calls: at most kHostCap envs, each array in a slot of its
+// own in the handle's staging buffers (Stage, below, which checks this size):
+// the most bytes per env one direction of one call stages (narde_host_step's
+// seven outputs) and each array's rounding to a slot.
+constexpr int64_t kHostCap = 4096;
+constexpr size_t kStageSlot = 256;
+constexpr size_t kStageEnvBytes = 130;
+constexpr size_t kStageArrays = 7;
+constexpr size_t kStageBytes = kHostCap * kStageEnvBytes + kStageArrays * kStageSlot;
+
+constexpr size_t stage_slot(size_t bytes) { return (bytes + kStageSlot - 1) & ~(kStageSlot - 1); }
 
 }  // namespace
 
@@ -92,7 +86,6 @@ struct narde_env {
   uint8_t* d_in;
   uint8_t* d_out;
   hipStream_t hstream;
-  size_t stage_bytes;
   // narde_turn_afterstates' workspace, made on its first call: the overflow
   // list [1 + n] and the overflow launches' frontier slab
   int32_t* turn_ovf;
@@ -110,25 +103,49 @@ Rng rng_of(const narde_env* e) {
   return g;
 }
 
-// the handle's device for the call; the caller's restored after it (no
-// runtime call on the way out when they are the same -- the usual case, and
-// the timed launch's host path)
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != d) switched = hipSetDevice(d) == hipSuccess;
+// k_step's arguments: n envs of planes pl (the handle's own or its host
+// envs), REF2 codes `actions` or a FULL4 `play`
+StepArgs step_args(const narde_env* e, const Planes& pl, int64_t n, int max_steps, int autoreset,
+                   const int16_t* actions, const int8_t* play, const uint8_t* dice, const Outs& out) {
+  return StepArgs{pl, (int)n, rng_of(e), max_steps, autoreset, actions, play, dice, out};
+}
+
+// One rollout launch: the kernel -- REF2's k_rollout_pc or FULL4's
+// producer/consumer pairs k_rollout_pp_full, in the
+// instantiation with per-ply outputs only when one is asked for -- its
+// geometry and its six arguments.  `last` is the output one rule set alone
+// has: REF2's codes used (int16_t[.][n][2]), FULL4's sub-moves (uint64_t[.][n]).
+struct RolloutLaunch {
+  const void* kernel;
+  const char* name;  // in a failed launch's error text
+  dim3 grid, block;
+  Planes pl;
+  int n;
+  Rng g;  // seed, env ids, dice law (the ply counter is each env's record word)
+  int plies;
+  int max_steps;
+  Outs out;
+  // hipLaunchKernel's argument array; valid while *this stays where it is
+  void bind(void* (&args)[6]) {
+    args[0] = &pl, args[1] = &n, args[2] = &g, args[3] = &plies, args[4] = &max_steps, args[5] = &out;
   }
-  ~DeviceGuard() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
+  int launch(hipStream_t stream) {
+    void* args[6];
+    bind(args);
+    (void)hipLaunchKernel(kernel, grid, block, args, 0, stream);
+    return check_launch(name);
   }
 };
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(NARDE_EHIP, "%s launch: %s", what, hipGetErrorString(e));
-  return NARDE_OK;
+RolloutLaunch rollout_launch(const narde_env* e, int full, int plies, int32_t* obs, int32_t* reward,
+                             uint8_t* terminated, uint8_t* truncated, uint64_t* legal, void* last, int64_t* totals) {
+  const bool any = obs || reward || terminated || truncated || legal || last;
+  return RolloutLaunch{full ? (any ? (const void*)k_rollout_pp_full<true> : (const void*)k_rollout_pp_full<false>)
+                            : (any ? (const void*)k_rollout_pc<true> : (const void*)k_rollout_pc<false>),
+                       full ? "k_rollout_pp_full" : "k_rollout", dim3((unsigned)((e->n + kPcEnvs - 1) / kPcEnvs)),
+                       dim3(kPcThreads), e->pl, (int)e->n, rng_of(e), plies, e->max_steps,
+                       Outs{obs, reward, terminated, truncated, legal, full ? nullptr : (int16_t*)last,
+                            full ? (uint64_t*)last : nullptr, totals}};
 }
 
 bool valid_position(const int8_t* board, const uint8_t* off, const uint8_t* ft, const int8_t* player,
@@ -155,8 +172,7 @@ int check_expand(const narde_env* e, int64_t cap, const int32_t* offsets, int ma
   if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
   if (e->n * (int64_t)max_rows >= (int64_t(1) << 31))
     return fail(NARDE_EINVAL, "too many envs for 32-bit row offsets (B x %d must stay below 2^31)", max_rows);
-  if ((reinterpret_cast<uintptr_t>(feat) % 16) || (reinterpret_cast<uintptr_t>(obs) % 16) ||
-      (reinterpret_cast<uintptr_t>(column) % align))
+  if (!aligned16(feat) || !aligned16(obs) || (reinterpret_cast<uintptr_t>(column) % align))
     return fail(NARDE_EINVAL, "%s", misaligned);
   return NARDE_OK;
 }
@@ -184,11 +200,6 @@ int pick_rows(narde_env* e, const int32_t* offsets, const void* column, int64_t 
 }
 
 }  // namespace
-
-namespace narde_abi {
-// the other translation units' (dqn_learner.hip) way into narde_last_error()
-int set_error(int code, const char* what) { return fail(code, "%s", what); }
-}  // namespace narde_abi
 
 extern "C" {
 
@@ -219,7 +230,6 @@ int narde_create(int device, int64_t num_envs, int64_t env_id_offset, uint64_t s
   e->seed = seed;
   e->dice_mode = dice_mode;
   e->max_steps = max_episode_steps;
-  e->stage_bytes = (size_t)kHostCap * 512;
   hipError_t err = hipSuccess;
   err = hipMalloc(&e->pl.p0, num_envs * sizeof(uint4));
   if (err == hipSuccess) err = hipMalloc(&e->pl.p1, num_envs * sizeof(uint4));
@@ -227,10 +237,10 @@ int narde_create(int device, int64_t num_envs, int64_t env_id_offset, uint64_t s
   if (err == hipSuccess) err = hipMalloc(&e->hpl.p0, kHostCap * sizeof(uint4));
   if (err == hipSuccess) err = hipMalloc(&e->hpl.p1, kHostCap * sizeof(uint4));
   if (err == hipSuccess) err = hipMalloc(&e->hpl.stats, kHostCap * sizeof(int4));
-  if (err == hipSuccess) err = hipMalloc(&e->d_in, e->stage_bytes);
-  if (err == hipSuccess) err = hipMalloc(&e->d_out, e->stage_bytes);
-  if (err == hipSuccess) err = hipHostMalloc(&e->h_in, e->stage_bytes, hipHostMallocDefault);
-  if (err == hipSuccess) err = hipHostMalloc(&e->h_out, e->stage_bytes, hipHostMallocDefault);
+  if (err == hipSuccess) err = hipMalloc(&e->d_in, kStageBytes);
+  if (err == hipSuccess) err = hipMalloc(&e->d_out, kStageBytes);
+  if (err == hipSuccess) err = hipHostMalloc(&e->h_in, kStageBytes, hipHostMallocDefault);
+  if (err == hipSuccess) err = hipHostMalloc(&e->h_out, kStageBytes, hipHostMallocDefault);
   if (err == hipSuccess) err = hipStreamCreateWithFlags(&e->hstream, hipStreamNonBlocking);
   if (err != hipSuccess) {
     narde_destroy(e);
@@ -341,17 +351,9 @@ int narde_step(narde_env* e, const int16_t* actions, const uint8_t* dice, int32_
                int16_t* actions_out, int autoreset, void* stream) {
   if (!e) return fail(NARDE_EINVAL, "NULL handle");
   DeviceGuard dg(e->device);
-  StepArgs a;
-  a.pl = e->pl;
-  a.n = (int)e->n;
-  a.g = rng_of(e);
-  a.max_steps = e->max_steps;
-  a.autoreset = autoreset;
-  a.actions = actions;
-  a.dice = dice;
-  a.play = nullptr;
-  a.out = Outs{obs, reward, terminated, truncated, legal_compact, actions_out, nullptr};
-  k_step<false><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(a);
+  k_step<false><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(
+      step_args(e, e->pl, e->n, e->max_steps, autoreset, actions, nullptr, dice,
+                Outs{obs, reward, terminated, truncated, legal_compact, actions_out, nullptr}));
   return check_launch("k_step");
 }
 
@@ -360,17 +362,9 @@ int narde_step_full(narde_env* e, const int8_t* play, const uint8_t* dice, int32
                     int autoreset, void* stream) {
   if (!e) return fail(NARDE_EINVAL, "NULL handle");
   DeviceGuard dg(e->device);
-  StepArgs a;
-  a.pl = e->pl;
-  a.n = (int)e->n;
-  a.g = rng_of(e);
-  a.max_steps = e->max_steps;
-  a.autoreset = autoreset;
-  a.actions = nullptr;
-  a.play = play;
-  a.dice = dice;
-  a.out = Outs{obs, reward, terminated, truncated, legal_first, nullptr, played};
-  k_step<true><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(a);
+  k_step<true><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(
+      step_args(e, e->pl, e->n, e->max_steps, autoreset, nullptr, play, dice,
+                Outs{obs, reward, terminated, truncated, legal_first, nullptr, played}));
   return check_launch("k_step<full>");
 }
 
@@ -378,37 +372,27 @@ int narde_step_full(narde_env* e, const int8_t* play, const uint8_t* dice, int32
 // hipEventRecord markers: hipExtLaunchKernel's packet-level start / stop
 // events were measured too and cost ~12 us more per host round trip of one
 // launch than the markers' ~4 us (tools/diag/single_launch.py, one box).
-namespace {
-
-int launch_rollout_ref2(narde_env* e, int plies, const Outs& out, bool any, hipStream_t stream) {
-  const dim3 g((unsigned)((e->n + kPcEnvs - 1) / kPcEnvs)), b(kPcThreads);
-  if (any)
-    k_rollout_pc<true><<<g, b, 0, stream>>>(e->pl, (int)e->n, rng_of(e), plies, e->max_steps, out);
-  else
-    k_rollout_pc<false><<<g, b, 0, stream>>>(e->pl, (int)e->n, rng_of(e), plies, e->max_steps, out);
-  return check_launch("k_rollout");
+int narde_rollout_timed(narde_env* e, int full, int plies, int32_t* obs, int32_t* reward, uint8_t* terminated,
+                        uint8_t* truncated, uint64_t* legal, void* last, void* ev_start, void* ev_stop,
+                        int64_t* totals, void* stream) {
+  if (!e || plies < 0) return fail(NARDE_EINVAL, "bad argument");
+  if (totals && plies == 0) return fail(NARDE_EINVAL, "totals rows need a launch (plies > 0)");
+  DeviceGuard dg(e->device);
+  RolloutLaunch l = rollout_launch(e, full, plies, obs, reward, terminated, truncated, legal, last, totals);
+  if (ev_start && hipEventRecord((hipEvent_t)ev_start, (hipStream_t)stream) != hipSuccess)
+    return fail(NARDE_EHIP, "hipEventRecord(ev_start) failed");
+  if (plies > 0)
+    if (const int rc = l.launch((hipStream_t)stream)) return rc;
+  if (ev_stop && hipEventRecord((hipEvent_t)ev_stop, (hipStream_t)stream) != hipSuccess)
+    return fail(NARDE_EHIP, "hipEventRecord(ev_stop) failed");
+  return NARDE_OK;
 }
-
-int launch_rollout_full(narde_env* e, int plies, const Outs& out, bool any, hipStream_t stream) {
-  // producer/consumer pairs (k_rollout_pp_full)
-  const dim3 g((unsigned)((e->n + kPcEnvs - 1) / kPcEnvs)), b(kPcThreads);
-  if (any)
-    k_rollout_pp_full<true><<<g, b, 0, stream>>>(e->pl, (int)e->n, rng_of(e), plies, e->max_steps, out);
-  else
-    k_rollout_pp_full<false><<<g, b, 0, stream>>>(e->pl, (int)e->n, rng_of(e), plies, e->max_steps, out);
-  return check_launch("k_rollout_pp_full");
-}
-
-}  // namespace
 
 int narde_rollout(narde_env* e, int plies, int32_t* obs, int32_t* reward, uint8_t* terminated,
                   uint8_t* truncated, uint64_t* legal_compact, int16_t* actions_out, void* stream) {
-  if (!e || plies < 0) return fail(NARDE_EINVAL, "bad argument");
-  if (plies == 0) return NARDE_OK;
-  DeviceGuard dg(e->device);
-  const Outs out{obs, reward, terminated, truncated, legal_compact, actions_out, nullptr};
-  const bool any = obs || reward || terminated || truncated || legal_compact || actions_out;
-  return launch_rollout_ref2(e, plies, out, any, (hipStream_t)stream);
+  if (e && plies == 0) return NARDE_OK;
+  return narde_rollout_timed(e, 0, plies, obs, reward, terminated, truncated, legal_compact, actions_out, nullptr,
+                             nullptr, nullptr, stream);
 }
 
 int narde_selfplay(narde_env* e, int plies, void* stream) {
@@ -417,39 +401,13 @@ int narde_selfplay(narde_env* e, int plies, void* stream) {
 
 int narde_rollout_full(narde_env* e, int plies, int32_t* obs, int32_t* reward, uint8_t* terminated,
                        uint8_t* truncated, uint64_t* legal_first, uint64_t* played, void* stream) {
-  if (!e || plies < 0) return fail(NARDE_EINVAL, "bad argument");
-  if (plies == 0) return NARDE_OK;
-  DeviceGuard dg(e->device);
-  const Outs out{obs, reward, terminated, truncated, legal_first, nullptr, played};
-  const bool any = obs || reward || terminated || truncated || legal_first || played;
-  return launch_rollout_full(e, plies, out, any, (hipStream_t)stream);
+  if (e && plies == 0) return NARDE_OK;
+  return narde_rollout_timed(e, 1, plies, obs, reward, terminated, truncated, legal_first, played, nullptr, nullptr,
+                             nullptr, stream);
 }
 
 int narde_selfplay_full(narde_env* e, int plies, void* stream) {
   return narde_rollout_full(e, plies, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-int narde_rollout_timed(narde_env* e, int full, int plies, int32_t* obs, int32_t* reward, uint8_t* terminated,
-                        uint8_t* truncated, uint64_t* legal, void* last, void* ev_start, void* ev_stop,
-                        int64_t* totals, void* stream) {
-  if (!e || plies < 0) return fail(NARDE_EINVAL, "bad argument");
-  if (totals && plies == 0) return fail(NARDE_EINVAL, "totals rows need a launch (plies > 0)");
-  DeviceGuard dg(e->device);
-  const bool any = obs || reward || terminated || truncated || legal || last;
-  if (ev_start && hipEventRecord((hipEvent_t)ev_start, (hipStream_t)stream) != hipSuccess)
-    return fail(NARDE_EHIP, "hipEventRecord(ev_start) failed");
-  int rc = NARDE_OK;
-  if (plies > 0 && full) {
-    const Outs out{obs, reward, terminated, truncated, legal, nullptr, (uint64_t*)last, totals};
-    rc = launch_rollout_full(e, plies, out, any, (hipStream_t)stream);
-  } else if (plies > 0) {
-    const Outs out{obs, reward, terminated, truncated, legal, (int16_t*)last, nullptr, totals};
-    rc = launch_rollout_ref2(e, plies, out, any, (hipStream_t)stream);
-  }
-  if (rc) return rc;
-  if (ev_stop && hipEventRecord((hipEvent_t)ev_stop, (hipStream_t)stream) != hipSuccess)
-    return fail(NARDE_EHIP, "hipEventRecord(ev_stop) failed");
-  return NARDE_OK;
 }
 
 // narde_rollout_timed pre-bound (round 6): everything but the launch is done
@@ -457,15 +415,7 @@ int narde_rollout_timed(narde_env* e, int full, int plies, int32_t* obs, int32_t
 // its arguments packed -- so the timed call is one ctypes argument and
 // three runtime calls (event, hipLaunchKernel, event), no device switch.
 struct narde_rollout_plan {
-  narde_env* e;
-  const void* kernel;
-  dim3 grid, block;
-  Planes pl;
-  int n;
-  Rng g;
-  int plies;
-  int max_steps;
-  Outs out;
+  RolloutLaunch l;
   void* args[6];
   hipEvent_t ev0, ev1;
   hipStream_t stream;
@@ -480,28 +430,8 @@ int narde_rollout_plan_create(narde_env* e, int full, int plies, int32_t* obs, i
     return fail(NARDE_EINVAL, "the calling thread's current device must be the env's");
   narde_rollout_plan* p = new (std::nothrow) narde_rollout_plan();
   if (!p) return fail(NARDE_ENOMEM, "out of host memory");
-  const bool any = obs || reward || terminated || truncated || legal || last;
-  if (full) {
-    p->out = Outs{obs, reward, terminated, truncated, legal, nullptr, (uint64_t*)last, totals};
-    p->kernel = any ? (const void*)k_rollout_pp_full<true> : (const void*)k_rollout_pp_full<false>;
-  } else {
-    p->out = Outs{obs, reward, terminated, truncated, legal, (int16_t*)last, nullptr, totals};
-    p->kernel = any ? (const void*)k_rollout_pc<true> : (const void*)k_rollout_pc<false>;
-  }
-  p->e = e;
-  p->grid = dim3((unsigned)((e->n + kPcEnvs - 1) / kPcEnvs));
-  p->block = dim3(kPcThreads);
-  p->pl = e->pl;
-  p->n = (int)e->n;
-  p->g = rng_of(e);  // seed, env ids, dice law (the ply counter is each env's record word)
-  p->plies = plies;
-  p->max_steps = e->max_steps;
-  p->args[0] = &p->pl;
-  p->args[1] = &p->n;
-  p->args[2] = &p->g;
-  p->args[3] = &p->plies;
-  p->args[4] = &p->max_steps;
-  p->args[5] = &p->out;
+  p->l = rollout_launch(e, full, plies, obs, reward, terminated, truncated, legal, last, totals);
+  p->l.bind(p->args);
   p->ev0 = (hipEvent_t)ev_start;
   p->ev1 = (hipEvent_t)ev_stop;
   p->stream = (hipStream_t)stream;
@@ -513,7 +443,7 @@ int narde_rollout_plan_launch(void* plan) {
   narde_rollout_plan* p = (narde_rollout_plan*)plan;
   if (!p) return fail(NARDE_EINVAL, "NULL plan");
   if (p->ev0 && hipEventRecord(p->ev0, p->stream) != hipSuccess) return fail(NARDE_EHIP, "hipEventRecord(ev_start) failed");
-  if (hipLaunchKernel(p->kernel, p->grid, p->block, p->args, 0, p->stream) != hipSuccess)
+  if (hipLaunchKernel(p->l.kernel, p->l.grid, p->l.block, p->args, 0, p->stream) != hipSuccess)
     return fail(NARDE_EHIP, "hipLaunchKernel(k_rollout) failed");
   if (p->ev1 && hipEventRecord(p->ev1, p->stream) != hipSuccess) return fail(NARDE_EHIP, "hipEventRecord(ev_stop) failed");
   return NARDE_OK;
@@ -770,7 +700,7 @@ int narde_head_policy576_dev(int device, const float* f, int64_t ldf, int64_t fe
     return fail(NARDE_EINVAL, "bad argument");
   if (ld_out < 1 || (out16 && ld_out16 < 1) || (addcol && ld_row < 1)) return fail(NARDE_EINVAL, "bad strides");
   if (feat != kHeadF || ldf < feat || ldw < feat || (ldf % 4) || (ldw % 4) ||
-      (reinterpret_cast<uintptr_t>(f) % 16) || (reinterpret_cast<uintptr_t>(w) % 16))
+      !aligned16(f) || !aligned16(w))
     return fail(NARDE_EINVAL, "features must be 256 wide, rows 16-B aligned");
   if (addcol && !add_row) return fail(NARDE_EINVAL, "addend column without its rows");
   if (n == 0) return NARDE_OK;
@@ -795,16 +725,77 @@ int narde_violates_block_rule(int device, const int8_t* boards, int64_t n, uint8
 // ------------------------------------------------------- host entry points
 namespace {
 
-struct Carve {
-  uint8_t* base;
-  size_t off = 0;
+// One narde_host_* call's staging.  An input has one offset in the pinned and
+// the device input buffer, an output one in the two output buffers; every
+// array starts on a kStageSlot boundary (the kernels read and write them as
+// they do device arrays: 16-byte row stores and the like).  The call declares
+// its arrays, then upload(), its launches, download(), and write_back() once
+// nothing can refuse the call any more.
+class Stage {
+ public:
+  explicit Stage(narde_env* e) : env(e) {}
+
+  // an input: count elements of the caller's src; returns the device copy
+  // (filled by upload())
   template <class T>
-  T* take(int64_t count) {
-    T* p = reinterpret_cast<T*>(base + off);
-    off += ((size_t)count * sizeof(T) + 255) & ~size_t(255);
-    return p;
+  const T* in(const T* src, int64_t count) {
+    const size_t at = in_, bytes = (size_t)count * sizeof(T);
+    in_ += stage_slot(bytes);
+    memcpy(env->h_in + at, src, bytes);
+    return reinterpret_cast<const T*>(env->d_in + at);
   }
+
+  // an output: returns the device array of count elements; write_back()
+  // copies them to the caller's dst (NULL: to nobody)
+  template <class T>
+  T* out(T* dst, int64_t count) {
+    const size_t at = out_, bytes = (size_t)count * sizeof(T);
+    out_ += stage_slot(bytes);
+    if (dst) back_[nback_++] = Back{dst, at, bytes};
+    return reinterpret_cast<T*>(env->d_out + at);
+  }
+
+  int upload() {
+    HIP_TRY(hipMemcpyAsync(env->d_in, env->h_in, in_, hipMemcpyHostToDevice, env->hstream));
+    return NARDE_OK;
+  }
+
+  // the outputs in pinned memory, the stream drained
+  int download() {
+    HIP_TRY(hipMemcpyAsync(env->h_out, env->d_out, out_, hipMemcpyDeviceToHost, env->hstream));
+    HIP_TRY(hipStreamSynchronize(env->hstream));
+    return NARDE_OK;
+  }
+
+  // a downloaded output, by its device array
+  template <class T>
+  const T* host(const T* dev) const {
+    return reinterpret_cast<const T*>(env->h_out + (reinterpret_cast<const uint8_t*>(dev) - env->d_out));
+  }
+
+  void write_back() const {
+    for (int k = 0; k < nback_; ++k) memcpy(back_[k].dst, env->h_out + back_[k].at, back_[k].bytes);
+  }
+
+ private:
+  struct Back { void* dst; size_t at, bytes; };
+  narde_env* env;
+  size_t in_ = 0, out_ = 0;
+  Back back_[kStageArrays];
+  int nback_ = 0;
 };
+
+// n envs of arrays of these bytes per env, staged; the calls' largest: the
+// outputs and the inputs of narde_host_step, narde_host_legal_moves' outputs
+constexpr size_t staged(int64_t n, std::initializer_list<int> env_bytes) {
+  size_t at = 0;
+  for (const int b : env_bytes) at += stage_slot((size_t)n * b);
+  return at;
+}
+static_assert(kStageArrays >= 7 && staged(kHostCap, {24, 2, 2, 1, 24 * 4, 4, 1}) <= kStageBytes &&
+                  staged(kHostCap, {24, 2, 2, 1, 2, 2 * 2}) <= kStageBytes &&
+                  staged(kHostCap, {2, NARDE_MAX_MOVES * 2}) <= kStageBytes,
+              "a narde_host_* call at kHostCap envs exceeds the staging buffers");
 
 int host_check(narde_env* e, int64_t n) {
   if (!e) return fail(NARDE_EINVAL, "NULL handle");
@@ -812,17 +803,37 @@ int host_check(narde_env* e, int64_t n) {
   return NARDE_OK;
 }
 
-int host_validate(int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* ft,
-                  const int8_t* player) {
+int host_validate(int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* ft, const int8_t* player) {
   for (int64_t i = 0; i < n; ++i)
     if (!valid_position(board, off, ft, player, i))
       return fail(NARDE_EINVAL, "invalid position at index %lld", (long long)i);
   return NARDE_OK;
 }
 
-int host_sync(narde_env* e) {
-  HIP_TRY(hipStreamSynchronize(e->hstream));
-  return NARDE_OK;
+// the position block of n envs, staged in; set(): into the handle's host
+// envs, once uploaded
+struct PositionIn {
+  const int8_t* board;
+  const uint8_t *off, *ft;
+  const int8_t* player;
+  void set(narde_env* e, int64_t n) const {
+    k_set_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, board, off, ft, player, nullptr, 0);
+  }
+};
+
+PositionIn stage_position(Stage& st, int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* ft,
+                          const int8_t* player) {
+  return PositionIn{st.in(board, n * 24), st.in(off, n * 2), st.in(ft, n * 2), st.in(player, n)};
+}
+
+// the host envs' position block read back into the caller's arrays (player
+// NULL: not read)
+void get_host_state(narde_env* e, Stage& st, int64_t n, int8_t* board, uint8_t* off, uint8_t* ft, int8_t* player) {
+  int8_t* db = st.out(board, n * 24);
+  uint8_t* doff = st.out(off, n * 2);
+  uint8_t* dft = st.out(ft, n * 2);
+  int8_t* dp = player ? st.out(player, n) : nullptr;
+  k_get_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db, doff, dft, dp, nullptr);
 }
 
 }  // namespace
@@ -838,25 +849,18 @@ int narde_host_legal_moves(narde_env* e, int64_t n, const int8_t* board, const u
   if (!board || !off || !ft || !player || !dice4 || !count) return fail(NARDE_EINVAL, "NULL argument");
   if ((rc = host_validate(n, board, off, ft, player))) return rc;
   DeviceGuard dg(e->device);
-  Carve hi{e->h_in}, di{e->d_in}, ho{e->h_out}, dq{e->d_out};
-  int8_t* hb = hi.take<int8_t>(n * 24); int8_t* db = di.take<int8_t>(n * 24);
-  uint8_t* hoff = hi.take<uint8_t>(n * 2); uint8_t* doff = di.take<uint8_t>(n * 2);
-  uint8_t* hft = hi.take<uint8_t>(n * 2); uint8_t* dft = di.take<uint8_t>(n * 2);
-  int8_t* hp = hi.take<int8_t>(n); int8_t* dp = di.take<int8_t>(n);
-  uint8_t* hd = hi.take<uint8_t>(n * 4); uint8_t* dd = di.take<uint8_t>(n * 4);
-  memcpy(hb, board, n * 24); memcpy(hoff, off, n * 2); memcpy(hft, ft, n * 2);
-  memcpy(hp, player, n); memcpy(hd, dice4, n * 4);
-  int16_t* hc = ho.take<int16_t>(n); int16_t* dc = dq.take<int16_t>(n);
-  int8_t* hm = ho.take<int8_t>(n * NARDE_MAX_MOVES * 2); int8_t* dm = dq.take<int8_t>(n * NARDE_MAX_MOVES * 2);
-  HIP_TRY(hipMemcpyAsync(e->d_in, e->h_in, hi.off, hipMemcpyHostToDevice, e->hstream));
-  k_set_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db, doff, dft, dp, nullptr, 0);
+  Stage st(e);
+  const PositionIn pos = stage_position(st, n, board, off, ft, player);
+  const uint8_t* dd = st.in(dice4, n * 4);
+  int16_t* dc = st.out(count, n);
+  int8_t* dm = st.out(moves, n * NARDE_MAX_MOVES * 2);
+  if ((rc = st.upload())) return rc;
+  pos.set(e, n);
   k_legal<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, rng_of(e), dd, dc, moves ? dm : nullptr,
                                               nullptr);
   if ((rc = check_launch("host legal"))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, dq.off, hipMemcpyDeviceToHost, e->hstream));
-  if ((rc = host_sync(e))) return rc;
-  memcpy(count, hc, n * sizeof(int16_t));
-  if (moves) memcpy(moves, hm, n * NARDE_MAX_MOVES * 2);
+  if ((rc = st.download())) return rc;
+  st.write_back();
   return NARDE_OK;
 }
 
@@ -871,43 +875,18 @@ int narde_host_step(narde_env* e, int64_t n, int8_t* board, uint8_t* off, uint8_
   for (int64_t i = 0; i < 2 * n; ++i)
     if (dice2[i] < 1 || dice2[i] > 6) return fail(NARDE_EINVAL, "die out of range at %lld", (long long)i);
   DeviceGuard dg(e->device);
-  Carve hi{e->h_in}, di{e->d_in}, ho{e->h_out}, dq{e->d_out};
-  int8_t* hb = hi.take<int8_t>(n * 24); int8_t* db = di.take<int8_t>(n * 24);
-  uint8_t* hoff = hi.take<uint8_t>(n * 2); uint8_t* doff = di.take<uint8_t>(n * 2);
-  uint8_t* hft = hi.take<uint8_t>(n * 2); uint8_t* dft = di.take<uint8_t>(n * 2);
-  int8_t* hp = hi.take<int8_t>(n); int8_t* dp = di.take<int8_t>(n);
-  uint8_t* hd = hi.take<uint8_t>(n * 2); uint8_t* dd = di.take<uint8_t>(n * 2);
-  int16_t* ha = hi.take<int16_t>(n * 2); int16_t* da = di.take<int16_t>(n * 2);
-  memcpy(hb, board, n * 24); memcpy(hoff, off, n * 2); memcpy(hft, ft, n * 2);
-  memcpy(hp, player, n); memcpy(hd, dice2, n * 2); memcpy(ha, actions, n * 4);
-  int8_t* hb2 = ho.take<int8_t>(n * 24); int8_t* db2 = dq.take<int8_t>(n * 24);
-  uint8_t* hoff2 = ho.take<uint8_t>(n * 2); uint8_t* doff2 = dq.take<uint8_t>(n * 2);
-  uint8_t* hft2 = ho.take<uint8_t>(n * 2); uint8_t* dft2 = dq.take<uint8_t>(n * 2);
-  int8_t* hp2 = ho.take<int8_t>(n); int8_t* dp2 = dq.take<int8_t>(n);
-  int32_t* hobs = ho.take<int32_t>(n * 24); int32_t* dobs = dq.take<int32_t>(n * 24);
-  int32_t* hr = ho.take<int32_t>(n); int32_t* dr = dq.take<int32_t>(n);
-  uint8_t* ht = ho.take<uint8_t>(n); uint8_t* dt = dq.take<uint8_t>(n);
-  HIP_TRY(hipMemcpyAsync(e->d_in, e->h_in, hi.off, hipMemcpyHostToDevice, e->hstream));
-  k_set_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db, doff, dft, dp, nullptr, 0);
-  StepArgs a;
-  a.pl = e->hpl;
-  a.n = (int)n;
-  a.g = rng_of(e);
-  a.max_steps = 0;
-  a.autoreset = 0;
-  a.actions = da;
-  a.dice = dd;
-  a.play = nullptr;
-  a.out = Outs{dobs, dr, dt, nullptr, nullptr, nullptr, nullptr};
-  k_step<false><<<grid(n), kBlock, 0, e->hstream>>>(a);
-  k_get_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db2, doff2, dft2, dp2, nullptr);
+  Stage st(e);
+  const PositionIn pos = stage_position(st, n, board, off, ft, player);
+  const uint8_t* dd = st.in(dice2, n * 2);
+  const int16_t* da = st.in(actions, n * 2);
+  const Outs out{st.out(obs, n * 24), st.out(reward, n), st.out(terminated, n), nullptr, nullptr, nullptr, nullptr};
+  if ((rc = st.upload())) return rc;
+  pos.set(e, n);
+  k_step<false><<<grid(n), kBlock, 0, e->hstream>>>(step_args(e, e->hpl, n, 0, 0, da, nullptr, dd, out));
+  get_host_state(e, st, n, board, off, ft, player);
   if ((rc = check_launch("host step"))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, dq.off, hipMemcpyDeviceToHost, e->hstream));
-  if ((rc = host_sync(e))) return rc;
-  memcpy(board, hb2, n * 24); memcpy(off, hoff2, n * 2); memcpy(ft, hft2, n * 2); memcpy(player, hp2, n);
-  if (obs) memcpy(obs, hobs, n * 24 * sizeof(int32_t));
-  if (reward) memcpy(reward, hr, n * sizeof(int32_t));
-  if (terminated) memcpy(terminated, ht, n);
+  if ((rc = st.download())) return rc;
+  st.write_back();
   return NARDE_OK;
 }
 
@@ -919,33 +898,25 @@ int narde_host_apply_moves(narde_env* e, int64_t n, int8_t* board, uint8_t* off,
   if (!board || !off || !ft || !player || !moves) return fail(NARDE_EINVAL, "NULL argument");
   if ((rc = host_validate(n, board, off, ft, player))) return rc;
   DeviceGuard dg(e->device);
-  Carve hi{e->h_in}, di{e->d_in}, ho{e->h_out}, dq{e->d_out};
-  int8_t* hb = hi.take<int8_t>(n * 24); int8_t* db = di.take<int8_t>(n * 24);
-  uint8_t* hoff = hi.take<uint8_t>(n * 2); uint8_t* doff = di.take<uint8_t>(n * 2);
-  uint8_t* hft = hi.take<uint8_t>(n * 2); uint8_t* dft = di.take<uint8_t>(n * 2);
-  int8_t* hp = hi.take<int8_t>(n); int8_t* dp = di.take<int8_t>(n);
-  int8_t* hm = hi.take<int8_t>(n * 2); int8_t* dm = di.take<int8_t>(n * 2);
-  memcpy(hb, board, n * 24); memcpy(hoff, off, n * 2); memcpy(hft, ft, n * 2);
-  memcpy(hp, player, n); memcpy(hm, moves, n * 2);
-  int8_t* hb2 = ho.take<int8_t>(n * 24); int8_t* db2 = dq.take<int8_t>(n * 24);
-  uint8_t* hoff2 = ho.take<uint8_t>(n * 2); uint8_t* doff2 = dq.take<uint8_t>(n * 2);
-  uint8_t* hft2 = ho.take<uint8_t>(n * 2); uint8_t* dft2 = dq.take<uint8_t>(n * 2);
-  uint8_t* hst = ho.take<uint8_t>(n); uint8_t* dst = dq.take<uint8_t>(n);
-  HIP_TRY(hipMemcpyAsync(e->d_in, e->h_in, hi.off, hipMemcpyHostToDevice, e->hstream));
-  k_set_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db, doff, dft, dp, nullptr, 0);
-  k_apply<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, dm, dp, dst);
-  k_get_state<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, db2, doff2, dft2, nullptr, nullptr);
+  Stage st(e);
+  const PositionIn pos = stage_position(st, n, board, off, ft, player);
+  const int8_t* dm = st.in(moves, n * 2);
+  uint8_t* status = st.out<uint8_t>(nullptr, n);
+  if ((rc = st.upload())) return rc;
+  pos.set(e, n);
+  k_apply<<<grid(n), kBlock, 0, e->hstream>>>(e->hpl, (int)n, dm, pos.player, status);
+  get_host_state(e, st, n, board, off, ft, nullptr);
   if ((rc = check_launch("host apply"))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, dq.off, hipMemcpyDeviceToHost, e->hstream));
-  if ((rc = host_sync(e))) return rc;
+  if ((rc = st.download())) return rc;
   // a move the record cannot hold (k_apply): nothing is written back
+  const uint8_t* refused = st.host(status);
   for (int64_t i = 0; i < n; ++i)
-    if (hst[i])
+    if (refused[i])
       return fail(NARDE_EINVAL,
                   "move (%d, %d) at index %lld is not executable: the source holds none of the "
                   "mover's checkers or the target holds opponent checkers",
                   (int)moves[2 * i], (int)moves[2 * i + 1], (long long)i);
-  memcpy(board, hb2, n * 24); memcpy(off, hoff2, n * 2); memcpy(ft, hft2, n * 2);
+  st.write_back();
   return NARDE_OK;
 }
 
@@ -955,16 +926,14 @@ int narde_host_violates_block_rule(narde_env* e, int64_t n, const int8_t* boards
   if (n == 0) return NARDE_OK;
   if (!boards || !out) return fail(NARDE_EINVAL, "NULL argument");
   DeviceGuard dg(e->device);
-  Carve hi{e->h_in}, di{e->d_in}, ho{e->h_out}, dq{e->d_out};
-  int8_t* hb = hi.take<int8_t>(n * 24); int8_t* db = di.take<int8_t>(n * 24);
-  memcpy(hb, boards, n * 24);
-  uint8_t* hr = ho.take<uint8_t>(n); uint8_t* dr = dq.take<uint8_t>(n);
-  HIP_TRY(hipMemcpyAsync(e->d_in, e->h_in, hi.off, hipMemcpyHostToDevice, e->hstream));
+  Stage st(e);
+  const int8_t* db = st.in(boards, n * 24);
+  uint8_t* dr = st.out(out, n);
+  if ((rc = st.upload())) return rc;
   k_block<<<grid(n), kBlock, 0, e->hstream>>>(db, (int)n, dr);
   if ((rc = check_launch("host block"))) return rc;
-  HIP_TRY(hipMemcpyAsync(e->h_out, e->d_out, dq.off, hipMemcpyDeviceToHost, e->hstream));
-  if ((rc = host_sync(e))) return rc;
-  memcpy(out, hr, n);
+  if ((rc = st.download())) return rc;
+  st.write_back();
   return NARDE_OK;
 }
 
