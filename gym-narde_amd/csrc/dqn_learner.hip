@@ -18,11 +18,12 @@
 //   + k_bias_grad_sum    sums of 64-row blocks, then the blocks in order);
 //   k_rowmax_addend    the target move-2 head's max over codes with the
 //                      one-hot column added on the fly;
-//   k_dqn_loss         targets, TD errors, the decomposed loss (:653-720) and
-//                      its gradient w.r.t. the two Q-values -- one block;
-//   k_prio_update      new priorities |td| + eps, the running max priority,
-//                      the per-update epsilon decay (:745-746) and the
-//                      step's cursor / tag advance -- one block;
+//   k_dqn_loss_prio    one block: the weights' normalisation, targets, TD
+//                      errors, the decomposed loss (:653-720) and its
+//                      gradient w.r.t. the two Q-values, new priorities
+//                      |td| + eps, the running max priority, the per-update
+//                      epsilon decay (:745-746) and the step's cursor / tag /
+//                      beta / counter advance;
 //   k_grad_sqnorm      clip_grad_norm_ + Adam: per-block squared-norm
 //   + k_adam           partials, then every block adds them in order.
 // Every scalar the driver updates per step (sampling counter, beta, max
@@ -43,8 +44,8 @@ namespace {
 
 constexpr int kLearnThreads = 1024;
 
-// block-wide max / sum over kLearnThreads threads (wave shuffles, then the
-// 16 wave results through LDS); every thread gets the result
+// block-wide max over kLearnThreads threads (wave shuffles, then the 16 wave
+// results through LDS); every thread gets the result
 __device__ __forceinline__ float block_max(float v, float* lds) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
@@ -54,20 +55,6 @@ __device__ __forceinline__ float block_max(float v, float* lds) {
   v = lane < kLearnThreads / 64 ? lds[lane] : -__builtin_inff();
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  return v;
-}
-
-// a fixed-order tree sum (deterministic from run to run)
-__device__ __forceinline__ float block_sum(float v, float* lds) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (lane == 0) lds[wave] = v;
-  __syncthreads();
-  v = lane < kLearnThreads / 64 ? lds[lane] : 0.0f;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   __syncthreads();
   return v;
 }
@@ -726,88 +713,21 @@ __global__ void __launch_bounds__(256) k_bias_grad_sum(const float* __restrict__
   if (qtr == 0 && col < cols) db[col] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
 }
 
-// --------------------------------------------------------------- the loss
-// t1 = r + (1 - d) * gamma * m1, t2 likewise (m = the target heads' maxima);
-// td = clamp(|t1 - q1| + |t2 - q2|, 0, 100); loss = mean(w (q1 - t1)^2) +
-// mean(w (q2 - t2)^2); g = dloss/dq = (1/B) * w * (2 (q - t)) in torch's
-// autograd order.  Each fp32 operation rounds on its own, as torch's
-// elementwise kernels do (no contraction).
-__global__ void __launch_bounds__(kLearnThreads) k_dqn_loss(const float* __restrict__ q1,
-                                                            const float* __restrict__ q2,
-                                                            const float* __restrict__ m1,
-                                                            const float* __restrict__ m2,
-                                                            const float* __restrict__ r,
-                                                            const float* __restrict__ d,
-                                                            const float* __restrict__ w, int batch,
-                                                            float gamma, float* __restrict__ td,
-                                                            float* __restrict__ loss,
-                                                            float* __restrict__ loss_copy,
-                                                            float* __restrict__ g1, float* __restrict__ g2) {
-#pragma clang fp contract(off)
-  __shared__ float red[kLearnThreads / 64];
-  const float inv_b = 1.0f / (float)batch;
-  float s1 = 0.0f, s2 = 0.0f;
-  for (int j = threadIdx.x; j < batch; j += kLearnThreads) {
-    const float nd = (1.0f - d[j]) * gamma;
-    const float t1 = r[j] + nd * m1[j];
-    const float t2 = r[j] + nd * m2[j];
-    const float e1 = q1[j] - t1, e2 = q2[j] - t2;
-    const float a = fabsf(t1 - q1[j]) + fabsf(t2 - q2[j]);
-    td[j] = fminf(fmaxf(a, 0.0f), 100.0f);
-    s1 += w[j] * (e1 * e1);
-    s2 += w[j] * (e2 * e2);
-    const float gw = inv_b * w[j];
-    g1[j] = gw * (2.0f * e1);
-    g2[j] = gw * (2.0f * e2);
-  }
-  s1 = block_sum(s1, red);
-  s2 = block_sum(s2, red);
-  if (threadIdx.x == 0) {
-    const float l = s1 / (float)batch + s2 / (float)batch;
-    *loss = l;
-    if (loss_copy) *loss_copy = l;
-  }
-}
-
-// ------------------------------------------------------ priorities, epsilon
-// prio[idx_j] = td_j + eps; max_prio = max(max_prio, max_j prio); then
-// epsilon <- epsilon * decay if epsilon > eps_min (one decay per update)
-__global__ void __launch_bounds__(kLearnThreads) k_prio_update(const int64_t* __restrict__ idx,
-                                                               const float* __restrict__ td, int batch,
-                                                               float eps, float* __restrict__ prio,
-                                                               float* __restrict__ max_prio,
-                                                               float* __restrict__ epsilon, float eps_min,
-                                                               float eps_decay, int64_t* __restrict__ cursor,
-                                                               int64_t cursor_add, int64_t cursor_mod,
-                                                               int64_t* __restrict__ tag) {
-  __shared__ float red[kLearnThreads / 64];
-  float m = -__builtin_inff();
-  for (int j = threadIdx.x; j < batch; j += kLearnThreads) {
-    const float pr = td[j] + eps;
-    prio[idx[j]] = pr;
-    m = fmaxf(m, pr);
-  }
-  m = block_max(m, red);
-  if (threadIdx.x == 0) {
-    *max_prio = fmaxf(*max_prio, m);
-    if (epsilon) {
-      const float e = *epsilon;
-      *epsilon = e > eps_min ? e * eps_decay : e;
-    }
-    // the driver's step bookkeeping, folded in (two torch launches fewer)
-    if (cursor) *cursor = (*cursor + cursor_add) % cursor_mod;
-    if (tag) *tag += 1;
-  }
-}
-
-// k_per_finish, k_dqn_loss and k_prio_update in one block (round 6; the
-// three were one-block kernels back to back): the batch max of the raw
-// importance weights (k_per_sample_gather's) and w_j / max written back to
-// w; the loss, td and dloss/dq exactly as k_dqn_loss; then the priorities,
-// the running max priority, epsilon, the write cursor and the step tag as
-// k_prio_update, and beta / the sampling counter as k_per_finish.  The
-// priorities move before the backward and Adam: nothing between reads them
-// (the next step's sample does).
+// ---------------------------------- the loss, priorities and bookkeeping
+// One block, raw importance weights in (k_per_sample_gather's):
+//   w_j <- w_j / max_j w (the max taken from 0), written back;
+//   t1 = r + (1 - d) * gamma * m1, t2 likewise (m = the target heads' maxima);
+//   td = clamp(|t1 - q1| + |t2 - q2|, 0, 100); loss = mean(w (q1 - t1)^2) +
+//   mean(w (q2 - t2)^2); g = dloss/dq = (1/B) * w * (2 (q - t)) in torch's
+//   autograd order -- each fp32 operation rounds on its own, as torch's
+//   elementwise kernels do (no contraction);
+//   prio[idx_j] = td_j + eps; max_prio = max(max_prio, max_j prio);
+//   epsilon <- epsilon * decay if epsilon > eps_min (one decay per update);
+//   the driver's step bookkeeping, when given: the replay ring's write
+//   cursor advanced by cursor_add rows and the step tag + 1;
+//   beta <- min(1, beta + beta_inc) and the sampling counter + 1.
+// The priorities move before the backward and Adam: nothing between reads
+// them (the next step's sample does).
 __global__ void __launch_bounds__(kLearnThreads) k_dqn_loss_prio(
     const float* __restrict__ q1, const float* __restrict__ q2, const float* __restrict__ m1,
     const float* __restrict__ m2, const float* __restrict__ r, const float* __restrict__ d, float* __restrict__ w,
@@ -838,7 +758,7 @@ __global__ void __launch_bounds__(kLearnThreads) k_dqn_loss_prio(
   float cw[kLossCache], cd[kLossCache], cr[kLossCache], cm1[kLossCache], cm2[kLossCache], cq1[kLossCache],
       cq2[kLossCache];
   int64_t ci[kLossCache];
-  // k_per_finish: the batch max (from 0, as there), then every w normalised
+  // the batch max (from 0), then every w normalised
   float wm = 0.0f;
 #pragma unroll
   for (int c = 0; c < kLossCache; ++c) {
@@ -883,8 +803,9 @@ __global__ void __launch_bounds__(kLearnThreads) k_dqn_loss_prio(
     prio[ij] = pr;
     pm = fmaxf(pm, pr);
   }
-  // block_sum(s1), block_sum(s2), block_max(pm) -- the same trees -- in one
-  // pass of barriers
+  // two fixed-order tree sums (deterministic from run to run) and a max in
+  // one pass of barriers: the waves' xor butterflies, then the same over
+  // the 16 wave results
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     s1 += __shfl_xor(s1, o, 64);
@@ -1084,10 +1005,6 @@ __global__ void __launch_bounds__(256) k_adam4(ParamTable t, const float* __rest
 
 }  // namespace
 
-// narde_adam_clip's form: float4 passes (default) or round 5's scalar ones
-// (narde_learner_variant, for A/B timing)
-static bool adam_vec4 = true;
-
 extern "C" {
 
 int narde_per_sample(int device, const float* p, const float* cdf, int64_t n, int64_t batch, uint64_t seed,
@@ -1196,31 +1113,6 @@ int narde_relu_bias_grad(int device, const float* gh, const float* h, int64_t n,
   return check_launch("k_bias_grad_sum");
 }
 
-int narde_dqn_loss(int device, const float* q1, const float* q2, const float* m1, const float* m2, const float* r,
-                   const float* d, const float* w, int64_t batch, float gamma, float* td, float* loss,
-                   float* loss_copy, float* g1, float* g2, void* stream) {
-  if (!q1 || !q2 || !m1 || !m2 || !r || !d || !w || !td || !loss || !g1 || !g2)
-    return fail(NARDE_EINVAL, "NULL argument");
-  if (batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "bad batch");
-  DeviceGuard dg(device);
-  k_dqn_loss<<<1, kLearnThreads, 0, (hipStream_t)stream>>>(q1, q2, m1, m2, r, d, w, (int)batch, gamma, td, loss,
-                                                           loss_copy, g1, g2);
-  return check_launch("k_dqn_loss");
-}
-
-int narde_prio_update(int device, const int64_t* idx, const float* td, int64_t batch, float eps, float* prio,
-                      float* max_prio, float* epsilon, float eps_min, float eps_decay, int64_t* cursor,
-                      int64_t cursor_add, int64_t cursor_mod, int64_t* tag, void* stream) {
-  if (!idx || !td || !prio || !max_prio) return fail(NARDE_EINVAL, "NULL argument");
-  if (batch <= 0 || batch > (int64_t(1) << 24)) return fail(NARDE_EINVAL, "bad batch");
-  if (cursor && (cursor_mod <= 0 || cursor_add < 0)) return fail(NARDE_EINVAL, "bad cursor step");
-  DeviceGuard dg(device);
-  k_prio_update<<<1, kLearnThreads, 0, (hipStream_t)stream>>>(idx, td, (int)batch, eps, prio, max_prio, epsilon,
-                                                              eps_min, eps_decay, cursor, cursor_add, cursor_mod,
-                                                              tag);
-  return check_launch("k_prio_update");
-}
-
 int narde_adam_clip(int device, int n_tensors, float* const* params, const float* const* grads, float* const* m,
                     float* const* v, const int64_t* sizes, int64_t* step, float lr, float beta1, float beta2,
                     float eps, float max_norm, float* scratch, void* stream) {
@@ -1243,10 +1135,12 @@ int narde_adam_clip(int device, int n_tensors, float* const* params, const float
   // scratch: kNormBlocks partial sums (the words after them are unused)
   float* partial = scratch;
   DeviceGuard dg(device);
-  bool vec = adam_vec4;
+  // one float4 per thread where every size and pointer allows, else the
+  // scalar passes
+  bool vec = true;
   for (int k = 0; k < n_tensors && vec; ++k)
     vec = sizes[k] % 4 == 0 && aligned16(params[k]) && aligned16(grads[k]) && aligned16(m[k]) && aligned16(v[k]);
-  if (vec) {  // one float4 per thread (round 6)
+  if (vec) {
     const int64_t total4 = total / 4;
     int nb4 = (int)((total4 + 255) / 256);
     nb4 = nb4 < kNormBlocks ? nb4 : kNormBlocks;
@@ -1314,14 +1208,6 @@ int narde_dqn_loss_prio(int device, const float* q1, const float* q2, const floa
                                                                 eps_min, eps_decay, cursor, cursor_add, cursor_mod,
                                                                 tag, counter, beta, beta_inc);
   return check_launch("k_dqn_loss_prio");
-}
-
-// A/B switch of the round-6 learner forms (tools, tests): bit 1 = the
-// float4 clip + Adam.  Returns the previous value.
-int narde_learner_variant(int flags) {
-  const int prev = adam_vec4 ? 2 : 0;
-  adam_vec4 = (flags & 2) != 0;
-  return prev;
 }
 
 }  // extern "C"

@@ -92,9 +92,9 @@ def expand_mask(mask576):
 def nearest_positive(p, idx):
     """A sampled row never has priority 0 (a pending row: its weight would be
     inf and the batch's weights NaN): where p[idx] == 0 take the last row
-    before idx with p > 0, else the first one after it -- k_per_sample's
-    rule.  Only a rounded-up u * total (the clamp to n - 1) or a prefix sum
-    whose flat run steps by an ulp can pick such a row."""
+    before idx with p > 0, else the first one after it -- the sampling
+    kernel's rule.  Only a rounded-up u * total (the clamp to n - 1) or a
+    prefix sum whose flat run steps by an ulp can pick such a row."""
     bad = ~(p[idx] > 0)  # (no host-side early exit: graph-capturable)
     n = p.shape[0]
     ar = torch.arange(n, device=p.device)
@@ -251,8 +251,9 @@ def rowmax_addend(base, tab, rows, out=None):
 
 def target_max2(nq1, base, tab, m1=None, am1=None, m2=None):
     """(m1, am1, m2): nq1.max(1) (values, indices: torch's rules -- NaN wins,
-    ties to the lowest code) and rowmax_addend(base, tab, am1) in one launch
-    (k_target_max2)."""
+    ties to the lowest code) and max_c base[i][c] + tab[am1[i]][c] over the
+    576 codes -- the target move-2 head's max without the (B,576) sum -- in
+    one launch (k_target_max2)."""
     n = nq1.shape[0]
     for t in (nq1, base, tab):
         if t.dtype != torch.float32 or t.stride(1) != 1 or t.shape[1] != MOVES:
@@ -265,12 +266,6 @@ def target_max2(nq1, base, tab, m1=None, am1=None, m2=None):
         nq1.device.index, _lib.ptr(nq1), nq1.stride(0), _lib.ptr(base), base.stride(0), _lib.ptr(tab), tab.stride(0),
         n, _f32(m1), _lib.ptr(am1), _f32(m2), _stream(nq1.device)), "narde_target_max2")
     return m1, am1, m2
-
-
-def learner_variant(flags):
-    """narde_learner_variant: bit 1 = the float4 clip + Adam (default), else
-    round 5's scalar passes; returns the previous flags."""
-    return int(_lib.load().narde_learner_variant(int(flags)))
 
 
 class GatheredHeads(torch.autograd.Function):
@@ -373,41 +368,12 @@ def features_fused(model, x, scratch):
     return LinearReLU.apply(h, l2.weight, l2.bias, scratch)
 
 
-class DQNLoss(torch.autograd.Function):
-    """The decomposed loss of train_deepq_pytorch.py:653-720 as one kernel
-    (k_dqn_loss): forward returns the loss and writes the TD errors into
-    `td`; the saved dloss/dq1, dloss/dq2 make the backward one multiply."""
-
-    @staticmethod
-    def compute(q1, q2, m1, m2, r, d, w, gamma, td, loss_copy):
-        """(loss, dloss/dq1, dloss/dq2) without autograd: the learner hands
-        the gradients to torch.autograd.backward((q1, q2), (g1, g2)) itself
-        (the backward's `go * g` multiplies are two launches for go = 1)."""
-        B = q1.shape[0]
-        loss = torch.empty((), dtype=torch.float32, device=q1.device)
-        g1, g2 = torch.empty_like(q1), torch.empty_like(q2)
-        _lib.check(_lib.load().narde_dqn_loss(
-            q1.device.index, _f32(q1), _f32(q2), _f32(m1), _f32(m2), _f32(r), _f32(d), _f32(w), B,
-            float(gamma), _f32(td), _lib.ptr(loss), None if loss_copy is None else _f32(loss_copy),
-            _lib.ptr(g1), _lib.ptr(g2), _stream(q1.device)), "narde_dqn_loss")
-        return loss, g1, g2
-
-    @staticmethod
-    def forward(ctx, q1, q2, m1, m2, r, d, w, gamma, td, loss_copy):
-        loss, g1, g2 = DQNLoss.compute(q1, q2, m1, m2, r, d, w, gamma, td, loss_copy)
-        ctx.save_for_backward(g1, g2)
-        return loss
-
-    @staticmethod
-    def backward(ctx, go):
-        g1, g2 = ctx.saved_tensors
-        return go * g1, go * g2, None, None, None, None, None, None, None, None
-
-
 class FusedAdamClip:
     """clip_grad_norm_(max_norm) + torch.optim.Adam.step in two HIP kernels
-    (narde_adam_clip): the gradient norm over all tensors with a
-    deterministic last-block sum, then every element's clipped Adam update.
+    (narde_adam_clip): per-block partial sums of the gradient norm over all
+    tensors, then every block adds them in one fixed order (deterministic)
+    before its elements' clipped Adam update; float4 passes, or one element
+    per thread where a size or a pointer is not float4's.
     Same math as torch's Adam (lerp first moment, bias corrections from a
     device step counter), fp32; graph-capturable (all state on device)."""
 
@@ -552,7 +518,7 @@ class DeviceReplay:
     # ---- fused (HIP) learner path: the same rules, one kernel each
     def prefix(self, n):
         """(prio[:n] ** alpha, its inclusive prefix sum) in two launches
-        (narde_per_prefix, round 6; sample() keeps torch's pow + cumsum,
+        (narde_per_prefix; sample() keeps torch's pow + cumsum,
         equal up to the rounding of the sums' association)."""
         p = torch.empty(n, dtype=torch.float32, device=self.prio.device)
         cdf = torch.empty_like(p)
@@ -577,9 +543,11 @@ class DeviceReplay:
         return idx, w
 
     def sample_gather_fused(self, batch, seed):
-        """sample_fused + gather in one launch (k_per_sample_gather): (idx, w,
-        s, ns, a, r, d) with w UNNORMALISED -- loss_prio_fused normalises it
-        in place and steps beta and the sampling counter."""
+        """sample() and the minibatch rows in one launch (k_per_sample_gather)
+        after prefix(): the search and weights with the kernel's own device
+        Philox counter (`sample_ctr`); (idx, w, s, ns, a, r, d) with ns from
+        row next_index(idx) and w UNNORMALISED -- loss_prio_fused normalises
+        it in place and steps beta and the sampling counter."""
         n, ss = self.rows, self.obs.shape[1]
         p, cdf = self.prefix(n)
         z = dict(device=p.device)
@@ -598,18 +566,26 @@ class DeviceReplay:
         return idx, w, s, ns, a, r, d
 
     def loss_prio_fused(self, q1, q2, m1, m2, r, d, w, gamma, td, loss, idx, epsilon=None, eps_min=0.0,
-                        eps_decay=1.0, cursor_add=0, tag=None):
-        """DQNLoss.compute + update_fused + sample_fused's normalisation and
-        beta / counter steps in one block (k_dqn_loss_prio); w (raw, from
-        sample_gather_fused) is normalised in place.  Returns (g1, g2)."""
+                        eps_decay=1.0, cursor_add=0, tag=None, loss_copy=None):
+        """The decomposed loss of train_deepq_pytorch.py:653-720, update()
+        and sample()'s weight normalisation and beta step in one block
+        (k_dqn_loss_prio): w (raw, from sample_gather_fused) is normalised
+        in place, the TD errors go to `td`, the loss to `loss` (and
+        `loss_copy`), the priorities of idx become td + epsilon; + the
+        driver's epsilon decay when an epsilon device scalar is given; + the
+        write cursor's advance by cursor_add rows and the driver's step tag
+        + 1, when given -- the step's bookkeeping folded into this launch;
+        the sampling counter + 1.  Returns (dloss/dq1, dloss/dq2): the
+        learner hands them to torch.autograd.backward((q1, q2), (g1, g2))
+        itself."""
         B = q1.shape[0]
         g1, g2 = torch.empty_like(q1), torch.empty_like(q2)
         _lib.check(_lib.load().narde_dqn_loss_prio(
             q1.device.index, _f32(q1), _f32(q2), _f32(m1), _f32(m2), _f32(r), _f32(d), _f32(w), B, float(gamma),
-            _f32(td), _lib.ptr(loss), None, _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(idx), float(self.epsilon),
-            _lib.ptr(self.prio), _lib.ptr(self.max_prio), None if epsilon is None else _lib.ptr(epsilon),
-            float(eps_min), float(eps_decay), _lib.ptr(self.pos_t) if cursor_add else None, int(cursor_add),
-            self.capacity, _lib.ptr(tag), _lib.ptr(self.sample_ctr), _lib.ptr(self.beta_t), float(self.beta_increment),
+            _f32(td), _lib.ptr(loss), _lib.ptr(loss_copy), _lib.ptr(g1), _lib.ptr(g2), _lib.ptr(idx),
+            float(self.epsilon), _lib.ptr(self.prio), _lib.ptr(self.max_prio), _lib.ptr(epsilon), float(eps_min),
+            float(eps_decay), _lib.ptr(self.pos_t) if cursor_add else None, int(cursor_add), self.capacity,
+            _lib.ptr(tag), _lib.ptr(self.sample_ctr), _lib.ptr(self.beta_t), float(self.beta_increment),
             _stream(q1.device)), "narde_dqn_loss_prio")
         return g1, g2
 
@@ -629,17 +605,6 @@ class DeviceReplay:
             _lib.ptr(a), _lib.ptr(r), _lib.ptr(d), _stream(self.obs.device)), "narde_gather_batch")
         return s, ns, a, r, d
 
-    def update_fused(self, idx, td, epsilon=None, eps_min=0.0, eps_decay=1.0, cursor_add=0, tag=None):
-        """update() as k_prio_update (+ the driver's epsilon decay when an
-        epsilon device scalar is given; + the write cursor's advance by
-        cursor_add rows and the driver's step tag + 1, when given -- the
-        step's bookkeeping folded into this launch)."""
-        _lib.check(_lib.load().narde_prio_update(
-            idx.device.index, _lib.ptr(idx), _f32(td), idx.shape[0], float(self.epsilon), _lib.ptr(self.prio),
-            _lib.ptr(self.max_prio), None if epsilon is None else _lib.ptr(epsilon), float(eps_min),
-            float(eps_decay), _lib.ptr(self.pos_t) if cursor_add else None, int(cursor_add), self.capacity,
-            _lib.ptr(tag), _stream(idx.device)), "narde_prio_update")
-
 
 class BatchedDQNDriver:
     """B envs of DQN self-play on one GPU; one call of step() = one env step
@@ -652,13 +617,17 @@ class BatchedDQNDriver:
     can be captured once in a torch.cuda.CUDAGraph and replayed
     (capture_graph()); the replay then costs one launch instead of ~150.
     The target-network sync stays on the host (every target_update
-    updates, an in-place copy the graph reads)."""
+    updates, an in-place copy the graph reads).
+
+    fused=True (default): the transition and the learner run as HIP kernels
+    (_transition_fused, _update_fused); fused=False: their torch
+    restatements (_transition_torch, _update_torch), what the tests compare
+    the kernels against."""
 
     def __init__(self, env, obs="tesauro198", train_batch=4096, capacity=1 << 20,
                  learning_rate=1e-4, gamma=0.99, epsilon=1.0, epsilon_min=0.01,
                  epsilon_decay=0.995, target_update=10, updates_per_step=1, shaping=True,
-                 seed=0, fused=True, fused_heads=True, gathered_heads=True, fused_features=True,
-                 explore="plays", greedy="accepted", one_launch_chains=True):
+                 seed=0, fused=True, fused_heads=True, explore="plays", greedy="accepted"):
         if env.full:
             raise ValueError("the DQN driver plays the reference's (move1, move2) actions: rules='ref2'")
         if explore not in ("plays", "codes"):
@@ -701,14 +670,6 @@ class BatchedDQNDriver:
         self.fused_learner = bool(fused)
         # the policy heads computed in the policy kernel (legal codes only)
         self.fused_heads = bool(fused_heads)
-        # the fused learner's online heads at the stored codes only
-        # (GatheredHeads) instead of dense heads + gather
-        self.gathered_heads = bool(gathered_heads)
-        # ... and its feature layers' ReLU mask + bias gradients in one kernel
-        # each (LinearReLU)
-        self.fused_features = bool(fused_features)
-        # round 6: the learner's one-block / one-launch chains (_update_fused6)
-        self.one_launch_chains = bool(one_launch_chains)
         self._rb_scratch = relu_bias_grad_scratch(self.train_batch, 256, self.dev)
         self.seed = seed
         self.tag_t = torch.zeros((), dtype=torch.int64, **z)
@@ -822,7 +783,7 @@ class BatchedDQNDriver:
         actions = self.act(x)
         _, reward, term, trunc, info = self.env.step(actions.to(torch.int16))
         # when the fused learner runs this step, the ring cursor's advance and
-        # the step tag's increment ride in its last kernel (k_prio_update)
+        # the step tag's increment ride in its one-block kernel (k_dqn_loss_prio)
         n, rp = self.env.num_envs, self.replay
         if self.fused:
             self._transition_fused(actions, reward, term, trunc, info["legal"], advance_cursor=False)
@@ -947,50 +908,15 @@ class BatchedDQNDriver:
 
     def _update_fused(self):
         """_update_torch with the non-GEMM chains as HIP kernels
-        (csrc/dqn_learner.hip): sample, gather, target move-2 max, loss +
-        grads, priorities + epsilon.  ~40 fewer launches per update.
-        one_launch_chains (round 6, default): sample + gather in one launch,
-        the target heads' max / argmax / move-2 max in one, and the weight
-        normalisation + loss + priorities + bookkeeping in one block."""
-        if self.one_launch_chains:
-            return self._update_fused6()
-        rp = self.replay
-        idx, w = rp.sample_fused(self.train_batch, self.seed)
-        s, ns, a, r, d = rp.gather(idx)
-        f = features_fused(self.model, s, self._rb_scratch) if self.fused_features else self.model.features(s)
-        if self.gathered_heads:
-            q1, q2 = gathered_heads(self.model, f, a)
-        else:
-            q1 = self.model.move1_head(f).gather(1, a[:, :1]).squeeze(1)
-            q2 = self.model.move2_from_features(f, a[:, 0]).gather(1, a[:, 1:]).squeeze(1)
-        with torch.no_grad():
-            tf = self.target.features_nograd(ns)
-            m1, am1 = self.target.move1_head(tf).max(1)
-            wt = self.target.move2_head.weight
-            base2 = torch.nn.functional.linear(tf, wt[:, :256], self.target.move2_head.bias)
-            m2 = rowmax_addend(base2, self._target_onehot_rows(), am1)
-        td = torch.empty_like(r)
-        _, g1, g2 = DQNLoss.compute(q1.detach(), q2.detach(), m1, m2, r, d, w, self.gamma, td, self.loss_t)
-        self.fopt.zero_grad(set_to_none=True)
-        torch.autograd.backward((q1, q2), (g1, g2))  # = loss.backward(): dloss/dq from k_dqn_loss
-        self.fopt.step()  # clip_grad_norm_(10) + Adam
-        cursor_add, tag = self._fold if self._fold is not None else (0, None)
-        self._fold = None
-        rp.update_fused(idx, td, self.eps_t, self.epsilon_min, self.epsilon_decay, cursor_add=cursor_add, tag=tag)
-        if self._capturing:
-            return self.loss_t
-        self._after_update()
-        return self.loss_t
-
-    def _update_fused6(self):
+        (csrc/dqn_learner.hip), one launch each: sample + gather; the target
+        heads' max / argmax / move-2 max; the weight normalisation + loss +
+        grads + priorities + epsilon + bookkeeping in one block; the online
+        heads at the stored codes (GatheredHeads); the feature layers'
+        backward (LinearReLU); clip + Adam."""
         rp = self.replay
         idx, w, s, ns, a, r, d = rp.sample_gather_fused(self.train_batch, self.seed)
-        f = features_fused(self.model, s, self._rb_scratch) if self.fused_features else self.model.features(s)
-        if self.gathered_heads:
-            q1, q2 = gathered_heads(self.model, f, a)
-        else:
-            q1 = self.model.move1_head(f).gather(1, a[:, :1]).squeeze(1)
-            q2 = self.model.move2_from_features(f, a[:, 0]).gather(1, a[:, 1:]).squeeze(1)
+        f = features_fused(self.model, s, self._rb_scratch)
+        q1, q2 = gathered_heads(self.model, f, a)
         with torch.no_grad():
             tf = self.target.features_nograd(ns)
             nq1 = self.target.move1_head(tf)

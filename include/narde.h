@@ -523,30 +523,13 @@ int narde_dqn_heads_backward(int device, const float *g1, const float *g2, const
 int narde_relu_bias_grad(int device, const float *gh, const float *h, int64_t n, int64_t cols,
                          float *g, float *db, float *scratch, void *stream);
 
-/* The decomposed DQN loss (train_deepq_pytorch.py:653-720) on batch rows:
- * t = r + (1 - d) * gamma * m (m1/m2 the target heads' maxima), td =
- * clamp(|t1 - q1| + |t2 - q2|, 0, 100), *loss = mean(w (q1 - t1)^2) +
- * mean(w (q2 - t2)^2) (also to *loss_copy if non-NULL), g1/g2 = dloss/dq1,
- * dloss/dq2. */
-int narde_dqn_loss(int device, const float *q1, const float *q2, const float *m1, const float *m2,
-                   const float *r, const float *d, const float *w, int64_t batch, float gamma,
-                   float *td, float *loss, float *loss_copy, float *g1, float *g2, void *stream);
-
-/* prio[idx_j] = td_j + eps; *max_prio = max(*max_prio, max_j); then, if
- * epsilon is non-NULL, *epsilon *= eps_decay when *epsilon > eps_min; if
- * cursor is non-NULL, *cursor = (*cursor + cursor_add) % cursor_mod (the
- * replay ring's write cursor); if tag is non-NULL, *tag += 1 (the driver's
- * step tag) -- device scalars a step's bookkeeping advances. */
-int narde_prio_update(int device, const int64_t *idx, const float *td, int64_t batch, float eps,
-                      float *prio, float *max_prio, float *epsilon, float eps_min,
-                      float eps_decay, int64_t *cursor, int64_t cursor_add, int64_t cursor_mod,
-                      int64_t *tag, void *stream);
-
 /* torch.nn.utils.clip_grad_norm_(max_norm) + one torch.optim.Adam step
  * (train_deepq_pytorch.py's optimizer) over n_tensors <= 8 fp32 parameter
  * tensors (params/grads/m/v: arrays of n_tensors device pointers, sizes in
  * elements).  *step (device i64) is advanced first; scratch: >= 1026 floats
- * of device memory, its last word zero before the first call (left zero). */
+ * of device memory, its last word zero before the first call (left zero).
+ * float4 passes when every size is a multiple of 4 and every pointer 16-byte
+ * aligned, else one element per thread: the same update either way. */
 int narde_adam_clip(int device, int n_tensors, float *const *params, const float *const *grads,
                     float *const *m, float *const *v, const int64_t *sizes, int64_t *step, float lr,
                     float beta1, float beta2, float eps, float max_norm, float *scratch,
@@ -571,9 +554,17 @@ int narde_target_max2(int device, const float *nq1, int64_t ld1, const float *ba
                       const float *tab, int64_t ld_tab, int64_t n, float *m1, int64_t *am1,
                       float *m2, void *stream);
 
-/* One block: w[j] /= max_j w[j] (narde_per_sample's normalisation, in place),
- * then narde_dqn_loss, then narde_prio_update on the same td, then beta =
- * min(1, beta + beta_inc) and *counter += 1 (narde_per_sample's steps). */
+/* The decomposed DQN loss (train_deepq_pytorch.py:653-720) on batch rows and
+ * the bookkeeping of one update, in one block: w[j] /= max_j w[j] in place
+ * (w raw, from narde_per_sample_gather); t = r + (1 - d) * gamma * m (m1/m2
+ * the target heads' maxima), td = clamp(|t1 - q1| + |t2 - q2|, 0, 100),
+ * *loss = mean(w (q1 - t1)^2) + mean(w (q2 - t2)^2) (also to *loss_copy if
+ * non-NULL), g1/g2 = dloss/dq1, dloss/dq2; prio[idx_j] = td_j + eps,
+ * *max_prio = max(*max_prio, max_j); then, if epsilon is non-NULL, *epsilon
+ * *= eps_decay when *epsilon > eps_min; if cursor is non-NULL, *cursor =
+ * (*cursor + cursor_add) % cursor_mod (the replay ring's write cursor); if
+ * tag is non-NULL, *tag += 1 (the driver's step tag); beta = min(1, beta +
+ * beta_inc) and *counter += 1 (the sampler's device scalars). */
 int narde_dqn_loss_prio(int device, const float *q1, const float *q2, const float *m1,
                         const float *m2, const float *r, const float *d, float *w, int64_t batch,
                         float gamma, float *td, float *loss, float *loss_copy, float *g1, float *g2,
@@ -581,11 +572,6 @@ int narde_dqn_loss_prio(int device, const float *q1, const float *q2, const floa
                         float eps_min, float eps_decay, int64_t *cursor, int64_t cursor_add,
                         int64_t cursor_mod, int64_t *tag, int64_t *counter, double *beta,
                         double beta_inc, void *stream);
-
-/* A/B switch of narde_adam_clip's form: bit 1 = float4 passes where sizes
- * and pointers allow (default), else round 5's scalar passes.  Returns the
- * previous flags. */
-int narde_learner_variant(int flags);
 
 /* Stateless: Narde._violates_block_rule on n perspective boards i8[n][24]. */
 int narde_violates_block_rule(int device, const int8_t *boards, int64_t n, uint8_t *out,

@@ -359,53 +359,6 @@ def test_gather_batch_and_rowmax_addend_exact():
     assert torch.equal(rowmax_addend(base, tab, rows), (base + tab[rows]).max(1).values)
 
 
-def test_dqn_loss_kernel_vs_torch_autograd():
-    """k_dqn_loss: TD errors and dloss/dq bit-exact against torch's autograd
-    of the reference loss (batch a power of two), the loss to fp32 summation
-    order."""
-    from gym_narde.dqn import DQNLoss
-
-    B, gamma = 4096, 0.99
-    g = torch.Generator(device="cuda:0").manual_seed(9)
-    rnd = lambda: torch.randn(B, device="cuda:0", generator=g)  # noqa: E731
-    q1, q2, m1, m2 = rnd(), rnd(), rnd(), rnd()
-    r = (torch.rand(B, device="cuda:0", generator=g) < 0.1).float() * 2
-    d = (torch.rand(B, device="cuda:0", generator=g) < 0.2).float()
-    w = torch.rand(B, device="cuda:0", generator=g)
-    q1r, q2r = q1.clone().requires_grad_(), q2.clone().requires_grad_()
-    t1 = r + (1 - d) * gamma * m1
-    t2 = r + (1 - d) * gamma * m2
-    td_ref = torch.clamp((t1 - q1r).abs() + (t2 - q2r).abs(), 0.0, 100.0).detach()
-    loss_ref = (w * (q1r - t1) ** 2).mean() + (w * (q2r - t2) ** 2).mean()
-    loss_ref.backward()
-    q1f, q2f = q1.clone().requires_grad_(), q2.clone().requires_grad_()
-    td = torch.empty(B, device="cuda:0")
-    copy = torch.zeros((), device="cuda:0")
-    loss = DQNLoss.apply(q1f, q2f, m1, m2, r, d, w, gamma, td, copy)
-    loss.backward()
-    assert torch.equal(td, td_ref)
-    assert torch.equal(q1f.grad, q1r.grad) and torch.equal(q2f.grad, q2r.grad)
-    assert float(loss.detach()) == pytest.approx(float(loss_ref.detach()), rel=1e-6)
-    assert float(copy) == float(loss.detach())
-
-
-def test_prio_update_kernel_exact():
-    from gym_narde.dqn import DeviceReplay
-
-    rp = DeviceReplay(10000, 4, "cuda:0", stride=1)
-    g = torch.Generator(device="cuda:0").manual_seed(2)
-    idx = torch.randperm(10000, device="cuda:0", generator=g)[:4096]
-    td = torch.rand(4096, device="cuda:0", generator=g) * 7
-    eps = torch.full((), 0.5, device="cuda:0")
-    rp.update_fused(idx, td, eps, 0.01, 0.995)
-    pr = td + rp.epsilon
-    assert torch.equal(rp.prio[idx], pr)
-    assert float(rp.max_prio) == float(torch.maximum(torch.ones((), device="cuda:0"), pr.max()))
-    want = torch.where(torch.full((), 0.5, device="cuda:0") > 0.01,
-                       torch.full((), 0.5, device="cuda:0") * 0.995, torch.full((), 0.5, device="cuda:0"))
-    assert float(eps) == float(want)
-
-
 def test_fused_and_torch_learners_agree_on_one_update():
     """One update from the same state: the fused learner (its own sampler)
     and the torch restatement given the fused learner's minibatch produce
@@ -819,6 +772,77 @@ def _filled_replay(n=5000, ss=198, stride=1234, seed=5):
     return rp
 
 
+def _uniforms(seed, ctr, batch):
+    """The sampler's uniforms rebuilt on the host: u_j = the top 24 bits of
+    Philox4x32-10({ctr, j, 0, 7}, seed)'s first word / 2^24 (exact in fp32)."""
+    import oracle as O
+
+    key = (seed & 0xFFFFFFFF, seed >> 32)
+    r0 = np.array([O.philox((ctr, j, 0, 7), key)[0] >> 8 for j in range(batch)], dtype=np.float32)
+    return torch.from_numpy(r0 / np.float32(2 ** 24)).cuda()
+
+
+def test_per_sample_gather_vs_torch():
+    """k_per_sample_gather: for its uniforms u (rebuilt on the host) and its
+    own prefix sums, every idx is the 64-ary search's row (the first with
+    cdf > u * total); against torch's cumsum, idx == searchsorted(right=True)
+    clamped up to the rounding of the prefix sums; raw weights == (N p[idx] /
+    total)^-beta (fp32, 1 ulp of powf); beta and the counter left untouched
+    (the loss block steps them); the minibatch rows are the ring's."""
+    from gym_narde.dqn import DeviceReplay
+
+    n, B = 300000, 4096
+    rp = DeviceReplay(n, 4, "cuda:0", stride=1)
+    g = torch.Generator(device="cuda:0").manual_seed(3)
+    rp.prio.copy_(torch.rand(n, device="cuda:0", generator=g) * 3 + 0.01)
+    rp.prio[:1000] = 50.0  # a heavy head
+    rp.size = n
+    beta0 = float(rp.beta_t)
+    idx, w_raw, *_ = rp.sample_gather_fused(B, seed=11)
+    assert int(rp.sample_ctr) == 0 and float(rp.beta_t) == beta0
+    u = _uniforms(11, 0, B)
+    # the kernel's own prefix sums: exact for every sample, monotone or not
+    _, own = rp.prefix(n)
+    v = u * own[n - 1]
+    assert bool(((own[idx] > v) | (idx == n - 1)).all())
+    assert bool(((idx == 0) | (own[(idx - 1).clamp(min=0)] <= v)).all())
+    p = rp.prio ** rp.alpha
+    cdf = torch.cumsum(p, 0)
+    total = cdf[-1]
+    v = u * total
+    want = torch.searchsorted(cdf, v, right=True).clamp_(max=n - 1)
+    # the sampler's prefix sums (narde_per_prefix, chunked) and torch's
+    # cumsum (a rocPRIM look-back scan) sum in other associations, so they
+    # differ by rounding -- over 300,000 rows by more than the spacing of a
+    # few rows' sums here and there: a pick may differ only where v lies
+    # within rounding of a prefix sum
+    off = idx != want
+    assert float(off.double().mean()) < 0.05
+    lo = torch.minimum(idx, want)[off]
+    assert bool(((cdf[lo] - v[off]).abs() <= 1e-4 * total).all())
+    x = (n * (p[idx] / total)) ** (-beta0)
+    assert torch.allclose(w_raw / w_raw.max(), x / x.max(), rtol=2e-6, atol=0)
+    rp.sample_ctr.add_(1)
+    idx2, *_ = rp.sample_gather_fused(B, seed=11)
+    assert not torch.equal(idx, idx2)  # a new counter, new draws
+    # proportional to priority^alpha over many draws
+    counts = torch.zeros(n, device="cuda:0")
+    for _ in range(20):
+        rp.sample_ctr.add_(1)
+        i, *_ = rp.sample_gather_fused(B, seed=11)
+        counts += torch.bincount(i, minlength=n).float()
+    head = float(counts[:1000].sum() / counts.sum())
+    assert head == pytest.approx(float(p[:1000].sum() / total), rel=0.05)
+    assert int(rp.sample_ctr) == 21 and float(rp.beta_t) == beta0
+    # the minibatch: the sampled rows of a ring with pending rows
+    rp = _filled_replay()
+    idx, _, s, ns, a, r, d = rp.sample_gather_fused(4096, seed=21)
+    for got, src in ((s, rp.obs[idx]), (ns, rp.obs[(idx + rp.stride) % rp.capacity]), (a, rp.action[idx]),
+                     (r, rp.reward[idx]), (d, rp.done[idx])):
+        assert torch.equal(got, src)
+    assert bool((rp.prio[idx] > 0).all())
+
+
 def test_per_sample_gather_equals_sample_then_gather():
     """k_per_sample_gather == k_per_sample + k_per_finish + k_gather_batch:
     the same rows and minibatch, its raw weights normalised by their max are
@@ -860,110 +884,170 @@ def test_target_max2_vs_torch_max_and_rowmax():
     assert torch.equal(m1[~v.isnan()], v[~v.isnan()]) and bool(m1[v.isnan()].isnan().all())
     assert int(am1[5]) == 300 and int(am1[6]) == 17
     assert torch.equal(m2, rowmax_addend(base, tab, am1))
+    assert torch.equal(m2, (base + tab[am1]).max(1).values)
     # ties: the lowest code holding the row maximum
     rows = torch.arange(0, n, 7, device="cuda:0")
     first = (nq1[rows] == v[rows, None]).int().argmax(1)
     assert torch.equal(am1[rows], first)
 
 
-def test_loss_prio_block_equals_the_three_kernels():
-    """k_dqn_loss_prio == the weight normalisation, k_dqn_loss and
-    k_prio_update (+ beta / counter steps): td, dloss/dq, the loss, the
-    priorities, max priority, epsilon, cursor and tag, bit for bit."""
-    from gym_narde.dqn import DQNLoss
+def _block_sum_order(x):
+    """The sum of x (B,) f32 in k_dqn_loss_prio's order: thread t of 1,024
+    adds rows t, t + 1024, ... in sequence; the 64 lanes of each wave meet in
+    an xor butterfly (o = 32 .. 1); the same butterfly over the 16 wave sums
+    padded with zeros.  Every add one fp32 operation: lane 0's bits."""
+    lanes = torch.arange(64, device=x.device)
 
-    B, gamma = 4096, 0.99
-    rp = _filled_replay(n=20000, stride=64)
+    def butterfly(v):  # (waves, 64) -> lane 0 of each wave
+        for o in (32, 16, 8, 4, 2, 1):
+            v = v + v[:, lanes ^ o]
+        return v[:, 0]
+
+    pad = torch.zeros(-(-x.numel() // 1024) * 1024, device=x.device)
+    pad[:x.numel()] = x
+    s = torch.zeros(1024, device=x.device)
+    for row in pad.view(-1, 1024):
+        s = s + row
+    waves = torch.zeros(64, device=x.device)
+    waves[:16] = butterfly(s.view(16, 64))
+    return butterfly(waves.view(1, 64))[0]
+
+
+def test_loss_prio_block_vs_torch_autograd():
+    """k_dqn_loss_prio on raw importance weights: w / max written back, TD
+    errors and dloss/dq bit-exact against torch's autograd of the reference
+    loss (batch a power of two), the loss to fp32 summation order and bit for
+    bit in the kernel's own order; priorities td + eps, the running max
+    priority, the epsilon decay, the ring cursor, tag, sampling counter and
+    beta stepped; the loss copy."""
+    B, gamma, cap = 4096, 0.99, 20000
+    rp = _filled_replay(n=cap, stride=64)
     g = torch.Generator(device="cuda:0").manual_seed(12)
     rnd = lambda: torch.randn(B, device="cuda:0", generator=g)  # noqa: E731
     q1, q2, m1, m2 = rnd(), rnd(), rnd(), rnd()
     r = (torch.rand(B, device="cuda:0", generator=g) < 0.1).float() * 2
     d = (torch.rand(B, device="cuda:0", generator=g) < 0.2).float()
     w_raw = torch.rand(B, device="cuda:0", generator=g) * 5 + 0.1
-    idx = torch.randperm(20000 - 64, device="cuda:0", generator=g)[:B]
-    # the unfused sequence on copies
-    prio0, maxp0, ctr0, beta0 = rp.prio.clone(), rp.max_prio.clone(), rp.sample_ctr.clone(), rp.beta_t.clone()
-    pos0 = rp.pos_t.clone()
-    eps_a = torch.full((), 0.5, device="cuda:0")
-    tag_a = torch.zeros((), dtype=torch.int64, device="cuda:0")
+    idx = torch.randperm(cap - 64, device="cuda:0", generator=g)[:B]
+    # torch autograd of the reference loss on the normalised weights
     w_n = w_raw / w_raw.max()
-    td_a = torch.empty(B, device="cuda:0")
-    loss_a, g1a, g2a = DQNLoss.compute(q1, q2, m1, m2, r, d, w_n, gamma, td_a, None)
-    rp.update_fused(idx, td_a, eps_a, 0.01, 0.995, cursor_add=64, tag=tag_a)
-    prio_a, maxp_a, pos_a = rp.prio.clone(), rp.max_prio.clone(), rp.pos_t.clone()
-    # the fused block from the same state
-    rp.prio.copy_(prio0); rp.max_prio.copy_(maxp0); rp.pos_t.copy_(pos0)
-    eps_b = torch.full((), 0.5, device="cuda:0")
-    tag_b = torch.zeros((), dtype=torch.int64, device="cuda:0")
-    td_b = torch.empty(B, device="cuda:0")
-    loss_b = torch.empty((), device="cuda:0")
-    w_b = w_raw.clone()
-    g1b, g2b = rp.loss_prio_fused(q1, q2, m1, m2, r, d, w_b, gamma, td_b, loss_b, idx, eps_b, 0.01, 0.995,
-                                  cursor_add=64, tag=tag_b)
-    assert torch.equal(w_b, w_n)
-    assert torch.equal(td_b, td_a) and torch.equal(g1b, g1a) and torch.equal(g2b, g2a)
-    assert float(loss_b) == float(loss_a)
-    assert torch.equal(rp.prio, prio_a) and float(rp.max_prio) == float(maxp_a) and int(rp.pos_t) == int(pos_a)
-    assert float(eps_b) == float(eps_a) and int(tag_b) == int(tag_a) == 1
-    assert int(rp.sample_ctr) == int(ctr0) + 1
-    assert float(rp.beta_t) == min(1.0, float(beta0) + rp.beta_increment)
+    q1r, q2r = q1.clone().requires_grad_(), q2.clone().requires_grad_()
+    t1 = r + (1 - d) * gamma * m1
+    t2 = r + (1 - d) * gamma * m2
+    td_ref = torch.clamp((t1 - q1r).abs() + (t2 - q2r).abs(), 0.0, 100.0).detach()
+    loss_ref = (w_n * (q1r - t1) ** 2).mean() + (w_n * (q2r - t2) ** 2).mean()
+    loss_ref.backward()
+    with torch.no_grad():
+        loss_ord = _block_sum_order(w_n * (q1 - t1) ** 2) / B + _block_sum_order(w_n * (q2 - t2) ** 2) / B
+    rp.pos_t.fill_(cap - 10)  # the cursor wraps
+    maxp0, ctr0, beta0 = rp.max_prio.clone(), int(rp.sample_ctr), float(rp.beta_t)
+    eps = torch.full((), 0.5, device="cuda:0")
+    tag = torch.full((), 7, dtype=torch.int64, device="cuda:0")
+    td = torch.empty(B, device="cuda:0")
+    loss, copy = torch.empty((), device="cuda:0"), torch.zeros((), device="cuda:0")
+    w = w_raw.clone()
+    g1, g2 = rp.loss_prio_fused(q1, q2, m1, m2, r, d, w, gamma, td, loss, idx, eps, 0.01, 0.995, cursor_add=64,
+                                tag=tag, loss_copy=copy)
+    assert torch.equal(w, w_n) and torch.equal(td, td_ref)
+    assert torch.equal(g1, q1r.grad) and torch.equal(g2, q2r.grad)
+    assert float(loss) == pytest.approx(float(loss_ref.detach()), rel=1e-6)
+    assert float(loss) == float(loss_ord) and float(copy) == float(loss)
+    pr = td_ref + rp.epsilon
+    assert torch.equal(rp.prio[idx], pr)
+    assert float(rp.max_prio) == float(torch.maximum(maxp0, pr.max()))
+    half = torch.full((), 0.5, device="cuda:0")
+    assert float(eps) == float(torch.where(half > 0.01, half * 0.995, half))
+    assert int(rp.pos_t) == (cap - 10 + 64) % cap
+    assert int(tag) == 8 and int(rp.sample_ctr) == ctr0 + 1
+    assert float(rp.beta_t) == min(1.0, beta0 + rp.beta_increment)
+
+
+def _adam_pair(values, offset):
+    """Two parameter lists of the same values and a FusedAdamClip over the
+    second, whose .grad tensors are contiguous views `offset` floats into
+    larger buffers."""
+    from gym_narde.dqn import FusedAdamClip
+
+    a = [torch.nn.Parameter(v.detach().clone()) for v in values]
+    b = [torch.nn.Parameter(v.detach().clone()) for v in values]
+    bufs = [torch.zeros(p.numel() + offset, device="cuda:0") for p in b]
+    for q, buf in zip(b, bufs):
+        q.grad = buf[offset:].view(q.shape)
+    return a, b, FusedAdamClip(b, lr=1e-3, max_norm=10.0)
 
 
 def test_adam_float4_vs_scalar_kernels():
-    """narde_adam_clip's float4 passes (round 6) against round 5's scalar
-    ones: the same clipped Adam steps to fp32 rounding, both deterministic."""
-    import copy
-
-    from gym_narde.dqn import DecomposedDQN, FusedAdamClip, learner_variant
+    """narde_adam_clip's float4 passes against its scalar ones, reached by
+    its own dispatch (gradients one float off 16-byte alignment): the same
+    clipped Adam steps to fp32 rounding."""
+    from gym_narde.dqn import DecomposedDQN, FusedAdamClip
 
     torch.manual_seed(4)
-    a = DecomposedDQN(198).cuda()
-    b = copy.deepcopy(a)
-    fa = FusedAdamClip(a.parameters(), lr=1e-3, max_norm=10.0)
-    fb = FusedAdamClip(b.parameters(), lr=1e-3, max_norm=10.0)
+    a, b, fb = _adam_pair(list(DecomposedDQN(198).cuda().parameters()), offset=1)
+    fa = FusedAdamClip(a, lr=1e-3, max_norm=10.0)
     g = torch.Generator(device="cuda:0").manual_seed(6)
-    prev = learner_variant(2)
-    try:
-        for _ in range(3):
-            grads = [torch.randn(p.shape, device="cuda:0", generator=g) * 5 for p in a.parameters()]
-            for p, q, gr in zip(a.parameters(), b.parameters(), grads):
-                p.grad = gr.clone()
-                q.grad = gr.clone()
-            learner_variant(2)
-            fa.step()
-            learner_variant(0)
-            fb.step()
-    finally:
-        learner_variant(prev)
-    for p, q in zip(a.parameters(), b.parameters()):
+    for _ in range(3):
+        for p, q in zip(a, b):
+            p.grad = torch.randn(p.shape, device="cuda:0", generator=g) * 5
+            q.grad.copy_(p.grad)
+            assert p.grad.data_ptr() % 16 == 0 and q.grad.data_ptr() % 16 == 4 and q.grad.is_contiguous()
+        fa.step()
+        fb.step()
+    for p, q in zip(a, b):
         assert torch.allclose(p, q, rtol=1e-5, atol=1e-6)
     assert int(fa.step_t) == int(fb.step_t) == 3
 
 
-def test_one_launch_learner_equals_round5_learner():
-    """Two drivers from the same seed, one with round 6's one-launch chains
-    and one with round 5's: the same losses, priorities and parameters over
-    three updates (the fused chains compute the same fp32 values; only the
-    clip's norm sums in another order)."""
+def test_adam_scalar_kernels_on_ragged_size_vs_torch():
+    """A parameter tensor whose size is no multiple of 4 sends
+    narde_adam_clip to its scalar passes: == clip_grad_norm_(10) +
+    torch.optim.Adam over three steps, to fp32 rounding."""
+    g = torch.Generator(device="cuda:0").manual_seed(6)
+    values = [torch.randn(s, device="cuda:0", generator=g) * 0.1 for s in ((300, 33), (1001,), (64, 64))]
+    a, b, fb = _adam_pair(values, offset=0)
+    ref = torch.optim.Adam(a, lr=1e-3)
+    for _ in range(3):
+        for p, q in zip(a, b):
+            p.grad = torch.randn(p.shape, device="cuda:0", generator=g) * 5
+            q.grad.copy_(p.grad)
+        torch.nn.utils.clip_grad_norm_(a, max_norm=10.0)
+        ref.step()
+        fb.step()
+    for p, q in zip(a, b):
+        assert torch.allclose(p, q, rtol=1e-5, atol=1e-6)
+    assert int(fb.step_t) == 3
+
+
+def test_fused_learner_equals_torch_learner_over_three_updates():
+    """The fused driver and BatchedDQNDriver(fused=False) given the fused
+    driver's minibatches, from the same parameters and ring: the same losses
+    and parameters over three updates to fp32 rounding (Adam included), the
+    same epsilon; the sampling counter and beta stepped once per update."""
+    import copy
+
     from gym_narde.dqn import BatchedDQNDriver
     from gym_narde.vector import VecNardeEnv
 
-    drv = []
-    for one in (True, False):
-        env = VecNardeEnv(4096, device="cuda:0", seed=41)
-        drv.append(BatchedDQNDriver(env, capacity=1 << 14, train_batch=1024, seed=3, one_launch_chains=one))
-    losses = [[], []]
-    for _ in range(6):
-        for k, d in enumerate(drv):
-            l = d.step()
-            if l is not None:
-                losses[k].append(float(l))
-    torch.cuda.synchronize()
-    assert len(losses[0]) >= 2 and len(losses[0]) == len(losses[1])
-    for x, y in zip(*losses):
+    env = VecNardeEnv(4096, device="cuda:0", seed=41)
+    kw = dict(capacity=1 << 14, train_batch=1024, seed=3)
+    drv = BatchedDQNDriver(env, updates_per_step=0, **kw)
+    for _ in range(3):  # fill the ring; no update yet
+        drv.step()
+    ref = BatchedDQNDriver(env, fused=False, **kw)
+    ref.model.load_state_dict(drv.model.state_dict())
+    ref.target.load_state_dict(drv.target.state_dict())
+    ref.replay = copy.deepcopy(drv.replay)
+    rp = drv.replay
+    beta0 = float(rp.beta_t)
+    for _ in range(3):
+        # (the sampler steps nothing: the update below draws these rows again)
+        idx, w_raw, *_ = rp.sample_gather_fused(drv.train_batch, drv.seed)
+        ref.replay.sample = lambda batch, generator=None, idx=idx, w=w_raw / w_raw.max(): (idx, w)
+        x, y = float(drv.update()), float(ref.update())
         assert x == pytest.approx(y, rel=1e-4, abs=1e-6)
-    for (k, p), (_, q) in zip(drv[0].model.state_dict().items(), drv[1].model.state_dict().items()):
+    torch.cuda.synchronize()
+    for (k, p), (_, q) in zip(drv.model.state_dict().items(), ref.model.state_dict().items()):
         assert torch.allclose(p, q, rtol=1e-4, atol=1e-5), k
-    assert int(drv[0].replay.sample_ctr) == int(drv[1].replay.sample_ctr)
-    assert float(drv[0].replay.beta_t) == float(drv[1].replay.beta_t)
-    assert float(drv[0].eps_t) == float(drv[1].eps_t) and int(drv[0].tag_t) == int(drv[1].tag_t)
+    assert drv.train_steps == ref.train_steps == 3
+    assert int(rp.sample_ctr) == 3 and float(rp.beta_t) == pytest.approx(beta0 + 3 * rp.beta_increment)
+    assert float(drv.eps_t) == float(ref.eps_t) < 1.0

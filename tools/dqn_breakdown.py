@@ -7,7 +7,7 @@
 
 Splits every graph-replayed step of the trace (BatchedDQNDriver._step_body,
 gym_narde/dqn.py) at its env step: `act` = the kernels from the previous
-step's last learner kernel (k_prio_update, or round 6's k_adam4) up to k_step (the 65,536-row
+step's last learner kernel (k_adam4, or k_adam) up to k_step (the 65,536-row
 feature GEMMs, the two head-policy kernels, the masks, the exploration
 draw), `env` = k_step + k_dqn_transition, `update` = the rest (the 4,096-row
 learner: sampling, gathers, GEMMs, loss, gradients, clip + Adam, priority
@@ -42,9 +42,9 @@ def main():
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
     ks = [(r["Kernel_Name"], int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows]
     step_ix = [j for j, k in enumerate(ks) if "k_step<false>" in k[0]]
-    # a learner ends at k_prio_update (round 5) or at its clip + Adam
-    # (round 6: the priorities ride in k_dqn_loss_prio, before the backward)
-    prio_ix = [j for j, k in enumerate(ks) if "k_prio_update" in k[0] or "k_adam" in k[0]]
+    # a learner ends at its clip + Adam (the priorities ride in
+    # k_dqn_loss_prio, before the backward)
+    prio_ix = [j for j, k in enumerate(ks) if "k_adam" in k[0]]
     steps = []
     for s0, s1 in zip(step_ix, step_ix[1:]):
         before = [p for p in prio_ix if p < s0]
