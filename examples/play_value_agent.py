@@ -6,9 +6,12 @@ play the best one for them (white the largest value, black the smallest:
 the README's reward is "+1 if WHITE wins").  Everything per ply runs on the
 device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step
 (--rules full4: whole turns under the real rules, four sub-moves on doubles:
-turn_afterstates -> net -> pick_turn -> step).
+turn_afterstates -> net -> pick_turn -> step).  --fused: the net becomes a
+value_net.ValueMLP and the rows are scored inside the expansion
+(scored_afterstates / scored_turn_afterstates: one float a row, the 198-float
+rows never made).
 
-  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4]
+  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused]
 """
 import argparse
 import os
@@ -28,7 +31,7 @@ def make_net(seed, device):
     return net.to(device).eval()
 
 
-def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2"):
+def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False):
     import torch
 
     from gym_narde.value_play import ValuePlayer
@@ -38,6 +41,10 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
     net = make_net(seed, env.device)
     if weights:
         net.load_state_dict(torch.load(weights, map_location=env.device))
+    if fused:
+        from gym_narde.value_net import ValueMLP
+
+        net = ValueMLP.from_sequential(net)
     player = ValuePlayer(env, net, perspective="white")
     eps = torch.tensor(epsilon, dtype=torch.float32, device=env.device) if epsilon > 0 else None
     rows = 0
@@ -60,5 +67,6 @@ if __name__ == "__main__":
     ap.add_argument("--epsilon", type=float, default=0.0)
     ap.add_argument("--weights", default=None)
     ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
+    ap.add_argument("--fused", action="store_true")
     a = ap.parse_args()
-    main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules)
+    main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused)

@@ -50,8 +50,11 @@ struct alignas(16) AftScan {  // per wave, both passes
 
 // env e's rows (all lanes of the wave call it with the same e); returns the
 // number of rows.  kFill: write them from row a.offsets[e] on, below a.cap.
-template <bool kFill>
-__device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftStage* S) {
+// kScore (a fill with a.feat NULL): the rows' values under vn as well
+// (kernels_rows.h "the scored rows"; VS the wave's lists).
+template <bool kFill, bool kScore = false>
+__device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftStage* S, const ValNet* vn = nullptr,
+                                       ValStage* VS = nullptr) {
   const int lane = threadIdx.x & 63;
   const Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
   int d0, d1;
@@ -74,6 +77,11 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
   wave_lds_handoff();
   const int total = __builtin_amdgcn_readfirstlane((int)L.incl[63]);  // <= kAftMaxPlays; scalar: uniform loops
   const int64_t row0 = kFill ? (int64_t)a.offsets[e] : 0;
+  ValRoot vr;
+  if constexpr (kScore) {
+    if (total == 0) return 0;  // wave-uniform: no play, nothing to score
+    val_root(vr, *vn, *VS, a.pl.p0[e], a.pl.p1[e], lane);
+  }
   int nkept = 0;
   for (int c0 = 0; c0 < total; c0 += 64) {
     const bool act = c0 + lane < total;
@@ -109,6 +117,11 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
           S->rec[rank][0] = ra;
           S->rec[rank][1] = rb;
         }
+        if constexpr (kScore) {
+          uint4 ra, rb;
+          side_to_record(c, ra, rb);
+          val_stage_row(*vn, *VS, vr, rank, R, a.cap, ra, rb, rew);
+        }
         if (R < a.cap) {
           int c1, c2;
           play_codes(y, c1, c2);
@@ -118,6 +131,7 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
         }
       }
       if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + nkept, nnew, *S, lane);
+      if constexpr (kScore) val_score_rows(*vn, *VS, vr, a.cap, row0 + nkept, nnew, lane);
     }
     nkept += nnew;
     wave_lds_handoff();  // the keys, to the next chunk
@@ -139,6 +153,15 @@ __global__ void __launch_bounds__(kAftFillBlock) k_aft_fill(AftArgs a) {
   const int e = aft_wave_env(kAftFillBlock / 64);
   if (e >= a.n) return;
   aft_env<true>(a, e, scan[threadIdx.x >> 6], &stage[threadIdx.x >> 6]);
+}
+
+// k_aft_fill with the rows' values in place of their 198 floats (a.feat NULL)
+__global__ void __launch_bounds__(kAftFillBlock) k_aft_fill_scored(AftArgs a, ValNet vn) {
+  __shared__ AftScan scan[kAftFillBlock / 64];
+  __shared__ ValStage stage[kAftFillBlock / 64];
+  const int e = aft_wave_env(kAftFillBlock / 64);
+  if (e >= a.n) return;
+  aft_env<true, true>(a, e, scan[threadIdx.x >> 6], nullptr, &vn, &stage[threadIdx.x >> 6]);
 }
 
 }  // namespace

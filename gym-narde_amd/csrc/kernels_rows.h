@@ -9,8 +9,10 @@ namespace {
 // pass leaves env e's row count in offsets[e + 1], k_aft_scan turns the
 // counts into offsets, a fill pass writes env e's rows from offsets[e] on,
 // below cap -- the narrow outputs (aft_store_row, and the kind's own action
-// column) from the row's lane, the 198 floats through LDS (aft_flush_feat).
-// k_aft_pick chooses a row per env by value.  A wave works on one env.
+// column) from the row's lane, the 198 floats through LDS (aft_flush_feat)
+// or, in the scored fills, the row's value under a small MLP in their place
+// (val_score_rows).  k_aft_pick chooses a row per env by value.  A wave
+// works on one env.
 
 // ------------------------------------------------------------ wave helpers
 __device__ __forceinline__ int wave_scan_incl(int x, int lane) {
@@ -109,6 +111,120 @@ __device__ __forceinline__ void aft_flush_feat(float* __restrict__ feat, int64_t
     }
     wave_lds_handoff();  // the next rows are staged behind these reads
   }
+}
+
+// ------------------------------------------------------------ the scored rows
+// aft_flush_feat's sibling: instead of a row's 198
+// floats, its value under a 198 -> H -> 1 MLP -- one float.  The env's own
+// pre-activations are computed once (val_root); a row's are those plus its
+// few differing columns' weight rows (narde_rules.h val_row_list: the row's
+// lane lists them in LDS).  The rows are then scored kValRows at a time, 16
+// lanes a row, lane t of a row holding hidden units t, t + 16, ...: reads of
+// W1t rows through the cache (64 B a lane group and unit), the activation,
+// w2, a sum over the 16 lanes and one store.  The kernels are bound by the
+// number of instructions, not by memory: this layout keeps every lane busy
+// for any H, and a row costs about a quarter of what one row a wave did
+// (MEASUREMENT_LOG M.30).
+static_assert(kValHiddenMax == NARDE_VALUE_HIDDEN_MAX, "narde.h and narde_rules.h state the same bound");
+
+struct ValNet {
+  const float* __restrict__ w1t;  // [198][ld]
+  int64_t ld;
+  const float* __restrict__ b1;   // [hidden]
+  const float* __restrict__ w2;   // [hidden]
+  const float* __restrict__ b2;   // [1]
+  int hidden, hidden_act, out_act, perspective;
+  float* __restrict__ value;      // [cap]
+};
+
+struct alignas(16) ValStage {  // per wave, scored fill pass
+  uint2 list[64][kValRowSlots];  // the chunk's rows' column lists, by rank
+  uint2 root[kValRootSlots];     // the env's own columns
+  int cnt[64];                   // a row's list length; -1: a terminal row, its outcome is written
+};
+
+struct ValRoot {  // per lane: the env's record and pre-activations, the lane's weights
+  uint4 ra, rb;
+  float z[kValUnits], w2[kValUnits], b2;
+  int t, g, nu;
+};
+
+// the env's part of the scoring, once per env (all lanes, the same record)
+__device__ __forceinline__ void val_root(ValRoot& r, const ValNet& n, ValStage& S, const uint4& ra, const uint4& rb,
+                                         int lane) {
+  r.ra = ra;
+  r.rb = rb;
+  r.t = lane & (kValLanes - 1);
+  r.g = lane / kValLanes;
+  r.nu = (n.hidden + kValLanes - 1) / kValLanes;
+#pragma unroll
+  for (int i = 0; i < kValUnits; ++i) r.z[i] = r.w2[i] = 0.0f;  // (units past nu are never read)
+  wave_lds_handoff();  // (earlier reads of S.root are done)
+  {  // the record's columns: lane = item, the items' entries placed by a prefix sum
+    int col[4];
+    float val[4];
+    const int c = tes_item_nonzero(ra, rb, lane, col, val);
+    const int incl = wave_scan_incl(c, lane);
+    const int total = min(__builtin_amdgcn_readlane(incl, 63), kValRootSlots);  // 33 at most; the bounds guard
+    const int npad = (total + kValRootBatch - 1) / kValRootBatch * kValRootBatch;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j < c && incl - c + j < kValRootSlots) S.root[incl - c + j] = val_entry(col[j], val[j], n.ld);
+    if (total + lane < npad) S.root[total + lane] = make_uint2(0u, 0u);
+    wave_lds_handoff();
+    val_units(r.nu, [&](auto NU) {
+      val_root_part<NU.value>(S.root, npad, r.g, n.w1t, r.t, n.hidden, r.z);
+#pragma unroll
+      for (int i = 0; i < NU.value; ++i) {
+        const bool on = r.t + kValLanes * i < n.hidden;
+        // ((p0 + p1) + (p2 + p3)) + b1, the same bits in every lane group
+        const float pair = r.z[i] + __shfl_xor(r.z[i], kValLanes, 64);
+        r.z[i] = (pair + __shfl_xor(pair, 2 * kValLanes, 64)) + (on ? n.b1[r.t + kValLanes * i] : 0.0f);
+        r.w2[i] = on ? n.w2[r.t + kValLanes * i] : 0.0f;  // (0 past hidden: such a unit adds nothing)
+      }
+    });
+  }
+  r.b2 = n.b2[0];
+}
+
+// row R's (rank `rank` of its chunk) part, from the row's lane: its column
+// list staged -- a terminal row's empty, its outcome written (R < cap)
+__device__ __forceinline__ void val_stage_row(const ValNet& n, ValStage& S, const ValRoot& r, int rank, int64_t R,
+                                              int64_t cap, const uint4& ca, const uint4& cb, int rew) {
+  if (rew != 0) {
+    S.cnt[rank] = -1;
+    for (int k = 0; k < kValRowSlots; ++k) S.list[rank][k] = make_uint2(0u, 0u);
+    if (R < cap) n.value[R] = val_outcome(rew, (cb.z >> 10) & 1u, n.perspective);
+  } else {
+    S.cnt[rank] = val_row_list(r.ra, r.rb, ca, cb, n.ld, S.list[rank]);
+  }
+}
+
+// the values of the nnew rows a chunk staged -> value rows Rbase .. Rbase +
+// nnew - 1, below cap, kValRows rows at a time (a short batch repeats the
+// last row).  All lanes of the wave call it with the same arguments.
+__device__ __forceinline__ void val_score_rows(const ValNet& n, ValStage& S, const ValRoot& r, int64_t cap,
+                                               int64_t Rbase, int nnew, int lane) {
+  wave_lds_handoff();  // the lists, to every lane
+  const int64_t room = cap - Rbase;
+  const int nr = room < (int64_t)nnew ? (int)room : nnew;  // wave-uniform: the rest is past cap
+  val_units(r.nu, [&](auto NU) {
+    for (int q0 = 0; q0 < nr; q0 += kValRows) {
+      const int q = min(q0 + r.g, nr - 1);
+      const int cnt = S.cnt[q];
+      if (__ballot(cnt >= 0) == 0ull) continue;  // wave-uniform: terminal rows only
+      const bool more = __ballot(cnt > kValRowFirst) != 0ull;
+      float z[kValUnits];
+#pragma unroll
+      for (int i = 0; i < NU.value; ++i) z[i] = r.z[i];
+      val_row_z<NU.value>(S.list[q], more, n.w1t, r.t, n.hidden, z);
+      float part = val_lane_part<NU.value>(z, r.w2, n.hidden_act);
+#pragma unroll
+      for (int o = kValLanes / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+      if (r.t == 0 && q0 + r.g < nr && cnt >= 0) n.value[Rbase + q] = val_out_act(r.b2 + part, n.out_act);
+    }
+  });
+  wave_lds_handoff();  // the next chunk's lists are staged behind these reads
 }
 
 // ------------------------------------------------------------ counts -> offsets

@@ -79,9 +79,12 @@ struct alignas(16) TurnFrontLds {  // per wave, fast path
 // key: room + 2 keys of the level being built; pathA, pathB: the two level
 // buffers, room paths each.
 // kFill: write the rows from row a.offsets[e] on, below a.cap.
-template <bool kFill>
+// kScore (a fill with a.feat NULL): the rows' values under vn as well
+// (kernels_rows.h "the scored rows"; VS the wave's lists).
+template <bool kFill, bool kScore = false>
 __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt, uint32_t* pathA, uint32_t* pathB,
-                                        int room, TurnScan& L, AftStage* S) {
+                                        int room, TurnScan& L, AftStage* S, const ValNet* vn = nullptr,
+                                        ValStage* VS = nullptr) {
   const int lane = threadIdx.x & 63;
   const Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
   int d0, d1;
@@ -169,6 +172,11 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
   const int nrows = (two && level == 1 && nh1 > 0) ? nh1 : ncur;
   if constexpr (kFill) {
     const int64_t row0 = (int64_t)a.offsets[e];
+    ValRoot vr;
+    if constexpr (kScore) {
+      if (row0 >= a.cap) return nrows;  // wave-uniform: every row is past cap
+      val_root(vr, *vn, *VS, a.pl.p0[e], a.pl.p1[e], lane);
+    }
     for (int g0 = 0; g0 < nrows; g0 += 64) {
       if (row0 + g0 >= a.cap) break;  // wave-uniform: the rest is past cap
       const bool act = g0 + lane < nrows;
@@ -184,6 +192,13 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         S->rec[lane][0] = ra;
         S->rec[lane][1] = rb;
       }
+      if constexpr (kScore) {
+        if (act) {
+          uint4 ra, rb;
+          side_to_record(c, ra, rb);
+          val_stage_row(*vn, *VS, vr, lane, R, a.cap, ra, rb, rew);
+        }
+      }
       if (act && R < a.cap) {
         if (a.play) reinterpret_cast<uint64_t*>(a.play)[R] = turn_path_play(path, level, r.dh, r.dl);
         if (a.reward) a.reward[R] = (int8_t)rew;
@@ -191,6 +206,7 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         if (a.obs) store_obs(a.obs, (size_t)R, c);
       }
       if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + g0, min(64, nrows - g0), *S, lane);
+      if constexpr (kScore) val_score_rows(*vn, *VS, vr, a.cap, row0 + g0, min(64, nrows - g0), lane);
     }
   }
   return nrows;
@@ -219,6 +235,18 @@ __global__ void __launch_bounds__(kTurnFillBlock) k_turn_fill(TurnArgs a) {
   // an env the count pass sent to the overflow list leaves here as it did
   // there, before it writes anything
   turn_env<true>(a, e, F.key, F.path[0], F.path[1], kTurnFront, scan[threadIdx.x >> 6], &stage[threadIdx.x >> 6]);
+}
+
+// k_turn_fill with the rows' values in place of their 198 floats (a.feat NULL)
+__global__ void __launch_bounds__(kTurnFillBlock) k_turn_fill_scored(TurnArgs a, ValNet vn) {
+  __shared__ TurnFrontLds front[kTurnFillBlock / 64];
+  __shared__ TurnScan scan[kTurnFillBlock / 64];
+  __shared__ ValStage stage[kTurnFillBlock / 64];
+  const int e = aft_wave_env(kTurnFillBlock / 64);
+  if (e >= a.n) return;
+  TurnFrontLds& F = front[threadIdx.x >> 6];
+  turn_env<true, true>(a, e, F.key, F.path[0], F.path[1], kTurnFront, scan[threadIdx.x >> 6], nullptr, &vn,
+                       &stage[threadIdx.x >> 6]);
 }
 
 // The overflow list's envs, a wave each, grid-stride.  First with a
@@ -253,6 +281,28 @@ __global__ void __launch_bounds__(64) k_turn_overflow(TurnArgs a) {
     }
     // (kTurnAftMax bounds every level: cnt < 0 cannot happen; the test is the bounds guard)
     if (!kFill && (threadIdx.x & 63) == 0) a.offsets[e + 1] = cnt < 0 ? 0 : cnt;
+    wave_lds_handoff();
+  }
+}
+
+// k_turn_overflow<true> with the rows' values in place of their 198 floats
+__global__ void __launch_bounds__(64) k_turn_overflow_scored(TurnArgs a, ValNet vn) {
+  __shared__ TurnScan scan;
+  __shared__ ValStage stage;
+  __shared__ TurnFrontBig big;
+  uint8_t* const base = a.slab + (size_t)blockIdx.x * kTurnSlabWave;
+  uint64_t* const key = reinterpret_cast<uint64_t*>(base);
+  uint32_t* const pathA = reinterpret_cast<uint32_t*>(key + kTurnSlabKeys);
+  uint32_t* const pathB = pathA + kTurnAftMax;
+  const int m = min(a.ovf[0], a.n);
+  for (int i = (int)blockIdx.x; i < m; i += (int)gridDim.x) {
+    const int e = __builtin_amdgcn_readfirstlane(a.ovf[1 + i]);
+    if ((unsigned)e >= (unsigned)a.n) continue;
+    int cnt = turn_env<true, true>(a, e, big.key, big.path[0], big.path[1], kTurnFrontBig, scan, nullptr, &vn, &stage);
+    if (cnt < 0) {  // wave-uniform
+      wave_lds_handoff();
+      turn_env<true, true>(a, e, key, pathA, pathB, kTurnAftMax, scan, nullptr, &vn, &stage);
+    }
     wave_lds_handoff();
   }
 }

@@ -18,11 +18,13 @@
 //   kernels_agent.h     observations, move masks, the policy kernel, the DQN
 //                       transition
 //   kernels_rows.h      afterstate rows, what both rule sets share: the wave
-//                       helpers, the row stores, k_aft_scan, k_aft_pick
+//                       helpers, the row stores, the scored rows (a value
+//                       MLP in the fill pass), k_aft_scan, k_aft_pick
 //   kernels_afterstates.h  REF2 afterstates: the play enumeration
-//                       (k_aft_count, k_aft_fill)
+//                       (k_aft_count, k_aft_fill, k_aft_fill_scored)
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
-//                       (k_turn_count, k_turn_fill, k_turn_overflow)
+//                       (k_turn_count, k_turn_fill, k_turn_overflow, and the
+//                       scored fills)
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip);
 // host_common.h: the host helpers the two share.
@@ -175,6 +177,85 @@ int check_expand(const narde_env* e, int64_t cap, const int32_t* offsets, int ma
   if (!aligned16(feat) || !aligned16(obs) || (reinterpret_cast<uintptr_t>(column) % align))
     return fail(NARDE_EINVAL, "%s", misaligned);
   return NARDE_OK;
+}
+
+// The scored expansions' (narde_afterstates_scored,
+// narde_turn_afterstates_scored) checks of the net, and the kernels' view of it.
+int check_value_net(const narde_value_mlp* net, int perspective, float* value, ValNet& vn) {
+  if (!net || !value) return fail(NARDE_EINVAL, "NULL argument");
+  if (!net->w1t || !net->b1 || !net->w2 || !net->b2) return fail(NARDE_EINVAL, "the net has a NULL weight array");
+  if (net->hidden < 1 || net->hidden > NARDE_VALUE_HIDDEN_MAX)
+    return fail(NARDE_EINVAL, "hidden %d outside 1..%d", (int)net->hidden, NARDE_VALUE_HIDDEN_MAX);
+  if (net->ld_w1t < net->hidden || net->ld_w1t > kValLdMax)
+    return fail(NARDE_EINVAL, "ld_w1t %lld outside hidden %d .. %lld", (long long)net->ld_w1t, (int)net->hidden,
+                (long long)kValLdMax);
+  if (net->hidden_act < 0 || net->hidden_act > 2 || net->out_act < 0 || net->out_act > 2)
+    return fail(NARDE_EINVAL, "activations: hidden 0 sigmoid, 1 tanh, 2 relu; out 0 none, 1 sigmoid, 2 tanh");
+  if (perspective != 0 && perspective != 1)
+    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
+  vn = ValNet{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act, net->out_act,
+              perspective, value};
+  return NARDE_OK;
+}
+
+// REF2's expansion: the count pass, the scan, and the fill -- with the
+// rows' values (vn) the scored one
+int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t st) {
+  const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
+  k_aft_count<<<(unsigned)((e->n + cw - 1) / cw), kAftCountBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_aft_count")) return rc;
+  k_aft_scan<<<1, kAftScanBlock, 0, st>>>(a.offsets, (int)e->n);
+  if (const int rc = check_launch("k_aft_scan")) return rc;
+  if (a.cap == 0 || !(a.row_env || a.codes || a.feat || a.obs || a.reward || vn)) return NARDE_OK;
+  if (vn) {
+    k_aft_fill_scored<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a, *vn);
+    return check_launch("k_aft_fill_scored");
+  }
+  k_aft_fill<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a);
+  return check_launch("k_aft_fill");
+}
+
+// FULL4's: the handle's workspace on its first call, the count passes, the
+// scan, the fills (scored with vn)
+int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env, int8_t* play,
+                 float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st) {
+  if (!e->turn_slab) {
+    // the workspace belongs to the handle and is made once, outside capture
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
+      return fail(NARDE_EINVAL, "the first narde_turn_afterstates call of a handle allocates its workspace: "
+                                "make it outside stream capture");
+    hipError_t err = hipMalloc(&e->turn_ovf, (size_t)(e->n + 1) * sizeof(int32_t));
+    if (err == hipSuccess) err = hipMalloc(&e->turn_slab, (size_t)kTurnOvfWaves * kTurnSlabWave);
+    if (err != hipSuccess) {
+      (void)hipFree(e->turn_ovf);
+      (void)hipFree(e->turn_slab);
+      e->turn_ovf = nullptr;
+      e->turn_slab = nullptr;
+      return fail(NARDE_ENOMEM, "turn afterstate workspace: %s", hipGetErrorString(err));
+    }
+  }
+  TurnArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, play, feat, obs, reward, e->turn_ovf,
+             e->turn_slab};
+  const int cw = kTurnCountBlock / 64, fw = kTurnFillBlock / 64;
+  HIP_TRY(hipMemsetAsync(e->turn_ovf, 0, sizeof(int32_t), st));
+  k_turn_count<<<(unsigned)((e->n + cw - 1) / cw), kTurnCountBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_count")) return rc;
+  k_turn_overflow<false><<<kTurnOvfWaves, 64, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_overflow<count>")) return rc;
+  k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
+  if (const int rc = check_launch("k_aft_scan")) return rc;
+  if (cap == 0 || !(row_env || play || feat || obs || reward || vn)) return NARDE_OK;
+  if (vn) {
+    k_turn_fill_scored<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a, *vn);
+    if (const int rc = check_launch("k_turn_fill_scored")) return rc;
+    k_turn_overflow_scored<<<kTurnOvfWaves, 64, 0, st>>>(a, *vn);
+    return check_launch("k_turn_overflow_scored");
+  }
+  k_turn_fill<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_turn_fill")) return rc;
+  k_turn_overflow<true><<<kTurnOvfWaves, 64, 0, st>>>(a);
+  return check_launch("k_turn_overflow<fill>");
 }
 
 // The two picks (narde_afterstate_pick, narde_turn_pick): the checks and the
@@ -595,15 +676,22 @@ int narde_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* o
                                   "feat and obs must be 16-B aligned, codes 4-B aligned"))
     return rc;
   DeviceGuard dg(e->device);
-  AftArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, feat, obs, reward};
-  const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
-  k_aft_count<<<(unsigned)((e->n + cw - 1) / cw), kAftCountBlock, 0, (hipStream_t)stream>>>(a);
-  if (const int rc = check_launch("k_aft_count")) return rc;
-  k_aft_scan<<<1, kAftScanBlock, 0, (hipStream_t)stream>>>(offsets, (int)e->n);
-  if (const int rc = check_launch("k_aft_scan")) return rc;
-  if (cap == 0 || !(row_env || codes || feat || obs || reward)) return NARDE_OK;
-  k_aft_fill<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, (hipStream_t)stream>>>(a);
-  return check_launch("k_aft_fill");
+  return expand_plays(e, AftArgs{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, feat, obs, reward},
+                      nullptr, (hipStream_t)stream);
+}
+
+int narde_afterstates_scored(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
+                             int16_t* codes, int8_t* reward, const narde_value_mlp* net, int perspective,
+                             float* value, void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, kAftMaxPlays, nullptr, nullptr, codes, 4,
+                                  "codes must be 4-B aligned"))
+    return rc;
+  ValNet vn;
+  if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
+  DeviceGuard dg(e->device);
+  return expand_plays(e, AftArgs{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, nullptr, nullptr,
+                                 reward},
+                      &vn, (hipStream_t)stream);
 }
 
 int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* codes, int64_t cap,
@@ -620,38 +708,19 @@ int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32
                                   "feat and obs must be 16-B aligned, play 8-B aligned"))
     return rc;
   DeviceGuard dg(e->device);
-  hipStream_t st = (hipStream_t)stream;
-  if (!e->turn_slab) {
-    // the workspace belongs to the handle and is made once, outside capture
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-      return fail(NARDE_EINVAL, "the first narde_turn_afterstates call of a handle allocates its workspace: "
-                                "make it outside stream capture");
-    hipError_t err = hipMalloc(&e->turn_ovf, (size_t)(e->n + 1) * sizeof(int32_t));
-    if (err == hipSuccess) err = hipMalloc(&e->turn_slab, (size_t)kTurnOvfWaves * kTurnSlabWave);
-    if (err != hipSuccess) {
-      (void)hipFree(e->turn_ovf);
-      (void)hipFree(e->turn_slab);
-      e->turn_ovf = nullptr;
-      e->turn_slab = nullptr;
-      return fail(NARDE_ENOMEM, "turn afterstate workspace: %s", hipGetErrorString(err));
-    }
-  }
-  TurnArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, play, feat, obs, reward, e->turn_ovf,
-             e->turn_slab};
-  const int cw = kTurnCountBlock / 64, fw = kTurnFillBlock / 64;
-  HIP_TRY(hipMemsetAsync(e->turn_ovf, 0, sizeof(int32_t), st));
-  k_turn_count<<<(unsigned)((e->n + cw - 1) / cw), kTurnCountBlock, 0, st>>>(a);
-  if (const int rc = check_launch("k_turn_count")) return rc;
-  k_turn_overflow<false><<<kTurnOvfWaves, 64, 0, st>>>(a);
-  if (const int rc = check_launch("k_turn_overflow<count>")) return rc;
-  k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
-  if (const int rc = check_launch("k_aft_scan")) return rc;
-  if (cap == 0 || !(row_env || play || feat || obs || reward)) return NARDE_OK;
-  k_turn_fill<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a);
-  if (const int rc = check_launch("k_turn_fill")) return rc;
-  k_turn_overflow<true><<<kTurnOvfWaves, 64, 0, st>>>(a);
-  return check_launch("k_turn_overflow<fill>");
+  return expand_turns(e, dice, cap, offsets, row_env, play, feat, obs, reward, nullptr, (hipStream_t)stream);
+}
+
+int narde_turn_afterstates_scored(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets,
+                                  int32_t* row_env, int8_t* play, int8_t* reward, const narde_value_mlp* net,
+                                  int perspective, float* value, void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, NARDE_TURN_AFT_MAX, nullptr, nullptr, play, 8,
+                                  "play must be 8-B aligned"))
+    return rc;
+  ValNet vn;
+  if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
+  DeviceGuard dg(e->device);
+  return expand_turns(e, dice, cap, offsets, row_env, play, nullptr, nullptr, reward, &vn, (hipStream_t)stream);
 }
 
 int narde_turn_pick(narde_env* e, const int32_t* offsets, const int8_t* play, int64_t cap, const float* value,

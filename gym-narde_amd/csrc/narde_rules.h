@@ -23,6 +23,7 @@
 // and in the test-only host build (tests/hostcheck).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 
 #define NARDE_FN __host__ __device__ __forceinline__
@@ -1971,6 +1972,252 @@ NARDE_FN float tes_value(uint4 a, uint4 b, int col) {
   const float board = j == 3 ? over : thr;
   const float pv = cc == 96 ? 0.0f : (cc == 97 ? offv : board);
   return col >= 196 ? player : pv;
+}
+
+// ------------------------------------------------- value MLP
+// v(row) = g_out(b2 + sum_h w2[h] g_hid(b1[h] + sum_c feat[c] W1t[c][h])) over
+// the 198 columns above, without the columns ever being written: a record's
+// non-zero columns and the columns in which two records differ come straight
+// from the nibbles, as (weight row, addend) pairs, and a hidden unit takes
+// them in list order.  Kernels (kernels_rows.h) and the host check
+// (tests/hostcheck/hostcheck_value.cpp) run these same functions.
+//
+// A wave scores kValRows rows at once, kValLanes lanes a row: lane t of a
+// row holds hidden units t, t + 16, ... (kValUnits at most).
+constexpr int kValHiddenMax = 128;
+constexpr int kValLanes = 16;
+constexpr int kValRows = 64 / kValLanes;
+constexpr int kValUnits = kValHiddenMax / kValLanes;
+constexpr int kValRowFirst = 6;   // a REF2 row: 4 moved-checker columns + the player one-hot
+constexpr int kValRowSlots = 10;  // a FULL4 row: 4 sources + 4 landings (or the off count) + the one-hot
+constexpr int kValRootEach = 4;   // a record's own columns: each of the kValRows lane groups takes every
+constexpr int kValRootBatch = kValRows * kValRootEach;  // fourth, kValRootEach to a batch
+constexpr int kValRootSlots = 48;  // 15 + 15 checkers' columns, two off counts, the player: 33, in batches
+constexpr int kValRootItems = 51;  // 24 points and the off count a side, the player
+constexpr int64_t kValLdMax = 1 << 20;  // a weight row's byte offset fits 32 bits
+
+// tes_value's values of a point's four columns (count v, column j) and of an
+// off count, by its own expressions
+NARDE_FN float tes_point_value(uint32_t v, int j) {
+  const float thr = v >= (uint32_t)(j + 1) ? 1.0f : 0.0f;
+  const float over = v >= 3u ? (float)(v - 3u) / 2.0f : 0.0f;
+  return j == 3 ? over : thr;
+}
+NARDE_FN float tes_off_value(uint32_t off) { return (float)off / 15.0f; }
+
+NARDE_FN uint32_t f32_bits(float x) { return __builtin_bit_cast(uint32_t, x); }
+NARDE_FN float bits_f32(uint32_t x) { return __builtin_bit_cast(float, x); }
+
+// the columns in which row (a1, b1) differs from root (a0, b0), ascending:
+// emit(col, old, new).  A side's nibble words XORed, the differing nibbles of
+// its 24 point counts walked, then its off nibble; last the mover bit.  A
+// count going u -> v changes at most |u - v| columns.  Returns their number.
+template <typename F>
+NARDE_FN int tes_delta_walk(const uint4& a0, const uint4& b0, const uint4& a1, const uint4& b1, F&& emit) {
+  int n = 0;
+  for (int side = 0; side < 2; ++side) {
+    const Nib r0{{side ? a0.z : a0.x, side ? a0.w : a0.y, side ? b0.y : b0.x}};
+    const Nib r1{{side ? a1.z : a1.x, side ? a1.w : a1.y, side ? b1.y : b1.x}};
+    const Nib x{{r0.w[0] ^ r1.w[0], r0.w[1] ^ r1.w[1], r0.w[2] ^ r1.w[2]}};
+    for (uint32_t m = nz_mask(x); m; m &= m - 1u) {
+      const int p = __builtin_ctz(m);
+      const uint32_t u = nib_get(r0, p), v = nib_get(r1, p);
+      const int col = 98 * side + 4 * p;
+      // the threshold columns between the two counts, then the fourth if
+      // either count is above 3: the columns whose tes_point_value differs
+      const uint32_t lo = u < v ? u : v, hi = u < v ? v : u;
+      for (int j = (int)lo; j < (int)(hi < 3u ? hi : 3u); ++j) {
+        emit(col + j, tes_point_value(u, j), tes_point_value(v, j));
+        ++n;
+      }
+      if (hi > 3u) {
+        emit(col + 3, tes_point_value(u, 3), tes_point_value(v, 3));
+        ++n;
+      }
+    }
+    const uint32_t u = (b0.z >> (4 * side)) & 15u, v = (b1.z >> (4 * side)) & 15u;
+    if (u != v) {
+      emit(98 * side + 97, tes_off_value(u), tes_off_value(v));
+      ++n;
+    }
+  }
+  const uint32_t k0 = (b0.z >> 10) & 1u, k1 = (b1.z >> 10) & 1u;
+  if (k0 != k1) {
+    emit(196, k0 ? 0.0f : 1.0f, k1 ? 0.0f : 1.0f);
+    emit(197, k0 ? 1.0f : 0.0f, k1 ? 1.0f : 0.0f);
+    n += 2;
+  }
+  return n;
+}
+
+// a record's non-zero columns, item by item in ascending column order: items
+// 0..23 white's points, 24 its off count, 25..48 black's points, 49 its off
+// count, 50 the player.  col[j], val[j], j < the count returned (4 at most:
+// a point's columns are non-zero from its first on).
+NARDE_FN int tes_item_nonzero(const uint4& a, const uint4& b, int item, int col[4], float val[4]) {
+  const int side = item >= 25 ? 1 : 0;
+  const int it = item - 25 * side;  // 0..23 a point, 24 the off count, (side 1) 25 the player
+  const Nib w{{side ? a.z : a.x, side ? a.w : a.y, side ? b.y : b.x}};
+  const uint32_t v = nib_get(w, it < 24 ? it : 0);
+  const uint32_t off = (b.z >> (4 * side)) & 15u;
+  const bool point = it < 24, player = it == 25;
+  const int npt = (int)(v < 3u ? v : 3u) + (v > 3u ? 1 : 0);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    col[j] = 98 * side + 4 * it + j;
+    val[j] = tes_point_value(v, j);
+  }
+  if (!point) {
+    col[0] = player ? 196 + (int)((b.z >> 10) & 1u) : 98 * side + 97;
+    val[0] = player ? 1.0f : tes_off_value(off);
+  }
+  return item >= kValRootItems ? 0 : (point ? npt : (player ? 1 : (off ? 1 : 0)));
+}
+
+// A list entry, what a hidden unit reads: the byte offset of the column's
+// weight row in W1t (feature-major, row stride ld floats) and the bits of
+// the addend.  Lists are padded with (0, 0.0f) -- an addend of zero leaves a
+// sum as it is -- so that they are taken in whole batches.
+NARDE_FN uint2 val_entry(int col, float addend, int64_t ld) {
+  return make_uint2((uint32_t)col * (uint32_t)(ld * 4), f32_bits(addend));  // (ld <= kValLdMax: 32 bits hold it)
+}
+// row against root: the addend is new - old; kValRowSlots entries.  Returns
+// the count (more than kValRowSlots cannot occur; the test is the bounds guard).
+NARDE_FN int val_row_list(const uint4& a0, const uint4& b0, const uint4& a1, const uint4& b1, int64_t ld, uint2* list) {
+  for (int k = 0; k < kValRowSlots; ++k) list[k] = make_uint2(0u, 0u);
+  int k = 0;
+  tes_delta_walk(a0, b0, a1, b1, [&](int col, float o, float nw) {
+    if (k < kValRowSlots) list[k++] = val_entry(col, nw - o, ld);
+  });
+  return k;
+}
+// a record's own columns, serially (the kernels place the items' entries by a
+// wave prefix sum instead); padded to the next multiple of kValRootBatch,
+// which is returned
+NARDE_FN int val_root_list(const uint4& a, const uint4& b, int64_t ld, uint2* list) {
+  int k = 0;
+  for (int item = 0; item < kValRootItems; ++item) {
+    int col[4];
+    float val[4];
+    const int c = tes_item_nonzero(a, b, item, col, val);
+    for (int j = 0; j < c; ++j)
+      if (k < kValRootSlots) list[k++] = val_entry(col[j], val[j], ld);
+  }
+  const int n = (k + kValRootBatch - 1) / kValRootBatch * kValRootBatch;
+  for (; k < n; ++k) list[k] = make_uint2(0u, 0u);
+  return n;
+}
+
+// lane t's hidden units t + 16 i, i < NU (NU = ceil(hidden / 16), the same
+// for every lane; val_units makes it a constant): z[i] += addend x
+// W1t[col][t + 16 i] over the N entries list[0], list[step], ..., in order,
+// one fused multiply-add each.  The N x NU weight reads go out together.
+template <int N, int NU>
+NARDE_FN void val_accumulate(const uint2* list, int step, const float* w1t, int t, int hidden,
+                             float (&z)[kValUnits]) {
+  float w[N][NU], d[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint2 ent = list[k * step];
+    const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(w1t) + ent.x) + t;
+    d[k] = bits_f32(ent.y);
+#pragma unroll
+    for (int i = 0; i < NU; ++i)
+      w[k][i] = (i + 1 < NU || t + kValLanes * i < hidden) ? p[kValLanes * i] : 0.0f;  // (only the last can be past hidden)
+  }
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) z[i] = fmaf(d[k], w[k][i], z[i]);
+  }
+}
+
+// f(std::integral_constant<int, nu>), nu = 1..kValUnits: the unit loops
+// unrolled for the net's size, chosen by one wave-uniform branch
+template <int K>
+struct ValUnits {
+  static constexpr int value = K;
+};
+template <typename F>
+NARDE_FN void val_units(int nu, F&& f) {
+  switch (nu) {
+    case 1: f(ValUnits<1>{}); break;
+    case 2: f(ValUnits<2>{}); break;
+    case 3: f(ValUnits<3>{}); break;
+    case 4: f(ValUnits<4>{}); break;
+    case 5: f(ValUnits<5>{}); break;
+    case 6: f(ValUnits<6>{}); break;
+    case 7: f(ValUnits<7>{}); break;
+    default: f(ValUnits<8>{}); break;
+  }
+}
+static_assert(kValUnits == 8, "val_units lists the cases");
+
+// A record's own pre-activations are summed in kValRows interleaved parts --
+// lane group g takes entries g, g + 4, g + 8, ... of its val_root_list (n
+// entries) -- joined as ((p0 + p1) + (p2 + p3)) + b1: val_root_part is one
+// group's part
+template <int NU>
+NARDE_FN void val_root_part(const uint2* list, int n, int g, const float* w1t, int t, int hidden,
+                            float (&z)[kValUnits]) {
+#pragma unroll
+  for (int i = 0; i < kValUnits; ++i) z[i] = 0.0f;
+  for (int k = 0; k < n; k += kValRootBatch)
+    val_accumulate<kValRootEach, NU>(list + k + g, kValRows, w1t, t, hidden, z);
+}
+// a row's, from its root's (z on entry) and its val_row_list; more: the list
+// (or that of another row of the batch) is longer than kValRowFirst
+template <int NU>
+NARDE_FN void val_row_z(const uint2* list, bool more, const float* w1t, int t, int hidden, float (&z)[kValUnits]) {
+  val_accumulate<kValRowFirst, NU>(list, 1, w1t, t, hidden, z);
+  if (more) val_accumulate<kValRowSlots - kValRowFirst, NU>(list + kValRowFirst, 1, w1t, t, hidden, z);
+}
+
+// exp and 1 / x: the device's one-instruction forms (1 ulp each; an
+// activation is a handful of instructions then, not the hundred and more of
+// the library's expf, tanhf and IEEE divide -- a wave instruction is four
+// cycles, and the scored fill is bound by their number)
+NARDE_FN float val_exp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f);
+#else
+  return expf(x);
+#endif
+}
+NARDE_FN float val_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcpf(x);
+#else
+  return 1.0f / x;
+#endif
+}
+NARDE_FN float val_sigmoid(float x) { return val_rcp(1.0f + val_exp(-x)); }
+NARDE_FN float val_tanh(float x) { return 1.0f - 2.0f * val_rcp(1.0f + val_exp(2.0f * x)); }
+// hidden: 0 sigmoid, 1 tanh, 2 relu; out: 0 none, 1 sigmoid, 2 tanh
+NARDE_FN float val_out_act(float y, int act) { return act == 0 ? y : (act == 1 ? val_sigmoid(y) : val_tanh(y)); }
+// lane t's part of the output sum: its units in order (w2t[i] = w2[t + 16 i],
+// 0 past hidden); the activation is chosen outside the unit loop
+template <int NU>
+NARDE_FN float val_lane_part(const float (&z)[kValUnits], const float (&w2t)[kValUnits], int act) {
+  float part = 0.0f;
+  if (act == 0) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) part += w2t[i] * val_sigmoid(z[i]);
+  } else if (act == 1) {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) part += w2t[i] * val_tanh(z[i]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < NU; ++i) part += w2t[i] * (z[i] > 0.0f ? z[i] : 0.0f);
+  }
+  return part;
+}
+// a terminal row's value: the step's reward for the side that moved (the
+// mover bit is not flipped after a terminal step), negated in white's
+// perspective (1) when that side is black
+NARDE_FN float val_outcome(int reward, uint32_t black, int perspective) {
+  const float r = (float)reward;
+  return perspective == 1 && black ? -r : r;
 }
 
 // ------------------------------------------------------------- Philox4x32-10

@@ -28,6 +28,14 @@ _i32 = ctypes.c_int
 _u32 = ctypes.c_uint32
 _u64 = ctypes.c_uint64
 
+
+
+class ValueMlp(ctypes.Structure):
+    """narde_value_mlp: device pointers of a 198 -> hidden -> 1 value net."""
+    _fields_ = [("w1t", _vp), ("ld_w1t", _i64), ("b1", _vp), ("w2", _vp), ("b2", _vp),
+                ("hidden", ctypes.c_int32), ("hidden_act", ctypes.c_int32), ("out_act", ctypes.c_int32)]
+
+
 # name -> (restype, argtypes); mirrors include/narde.h one to one
 SIGNATURES = {
     "narde_version": (_i32, []),
@@ -69,6 +77,9 @@ SIGNATURES = {
     "narde_afterstate_pick": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "narde_turn_afterstates": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_pick": (_i32, [_vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "narde_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp]),
+    "narde_turn_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
+                                             _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

@@ -8,6 +8,9 @@ everything on the device: VecNardeEnv.afterstates() expands the roll,
 `net` scores the rows, VecNardeEnv.pick_afterstate() chooses, step() plays.
 On a rules="full4" env the rows are whole turns (turn_afterstates(),
 pick_turn()): four sub-moves on doubles, the max-dice-used rule.
+With a value_net.ValueMLP the rows are scored inside the expansion
+(scored_afterstates() / scored_turn_afterstates(): one float a row, the
+198-float rows never made).
 """
 
 
@@ -16,9 +19,14 @@ class ValuePlayer:
     torch.nn.Module on the env's device).  perspective "white": the values
     are white's (the README's reward) -- white plays the largest, black the
     smallest; "mover": they are the side's that has just moved -- always the
-    largest."""
+    largest.
+    fused: None -- the scored expansion when net is a value_net.ValueMLP;
+    False -- never (every step as with any other module); True -- required
+    (a TypeError for another module).  cap: the rows every step's arrays
+    hold (fused only); with it a step makes no synchronise, and rows past
+    cap are not played."""
 
-    def __init__(self, env, net, perspective="white"):
+    def __init__(self, env, net, perspective="white", fused=None, cap=None):
         from .vector import PERSPECTIVES
 
         if perspective not in PERSPECTIVES:
@@ -26,6 +34,14 @@ class ValuePlayer:
         self.env, self.net, self.perspective = env, net, perspective
         self._expand, self._pick = ((env.turn_afterstates, env.pick_turn) if env.full else
                                     (env.afterstates, env.pick_afterstate))
+        is_mlp = hasattr(net, "struct") and hasattr(net, "pack")
+        if fused and not is_mlp:
+            raise TypeError("fused=True needs a gym_narde.value_net.ValueMLP")
+        self.fused = is_mlp if fused is None else bool(fused)
+        if cap is not None and not self.fused:
+            raise ValueError("cap is the fused path's")
+        self.cap = None if cap is None else int(cap)
+        self._scored = env.scored_turn_afterstates if env.full else env.scored_afterstates
 
     def values(self, aft):
         """net(feat), with the rows that end the game set to their known
@@ -49,11 +65,15 @@ class ValuePlayer:
         values, the pick, the step.  Returns (obs, reward, terminated,
         truncated, info, aft, values, actions); an env with no expressible
         play steps with (0, 0), which moves nothing (rules="full4": actions
-        are (B,4,2) plays, all -1 for an env that has to pass)."""
+        are (B,4,2) plays, all -1 for an env that has to pass).  On the fused
+        path aft.feat is None."""
         env = self.env
         dice = env.dice()
-        aft = self._expand(dice)
-        values = self.values(aft)
+        if self.fused:
+            aft, values = self._scored(self.net, dice, cap=self.cap, perspective=self.perspective)
+        else:
+            aft = self._expand(dice)
+            values = self.values(aft)
         actions, row = self._pick(aft, values, self.perspective, epsilon, tag, seed)
         obs, reward, terminated, truncated, info = env.step(actions)
         info = dict(info, dice=dice, row=row)

@@ -383,6 +383,85 @@ class VecNardeEnv:
         self._keep = (d,)
         return out._replace(cap=cap)
 
+    def _scored_rows(self, k, net, dice, cap, perspective, out):
+        """scored_afterstates() / scored_turn_afterstates(): the rows of kind
+        k with their values under net in place of feat and obs."""
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        B, t = self.num_envs, self.torch
+        if not hasattr(net, "struct"):
+            raise TypeError("net must be a gym_narde.value_net.ValueMLP")
+        mlp = net.struct()
+        if net.l1.weight.device != self.device:
+            raise ValueError("the net must live on the env's device")
+        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        values = None
+        if out is not None:
+            if not hasattr(out, "offsets"):
+                out, values = out
+            offsets = out.offsets
+            cap = out.cap if cap is None else int(cap)
+            if values is None:
+                values = t.empty(cap, dtype=t.float32, device=self.device)
+            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
+                                       (k.field, getattr(out, k.field), k.shape, getattr(t, k.dtype)),
+                                       ("reward", out.reward, (), t.int8), ("values", values, (), t.float32)):
+                if a is None and name != "values":
+                    continue
+                ok = a is not None and a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
+                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
+                if not ok:
+                    raise ValueError(f"out {name} must be a contiguous {dt} device tensor of at least cap rows")
+            out = out._replace(feat=None, obs=None)
+        else:
+            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
+            if cap is None:
+                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+                cap = int(offsets[B].item())  # the one synchronise
+            cap = int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            mk = lambda shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device)  # noqa: E731
+            out = k.tuple(offsets, mk((), t.int32), mk(k.shape, getattr(t, k.dtype)), None, None, mk((), t.int8), cap)
+            values = mk((), t.float32)
+        if cap < 0:
+            raise ValueError("cap must be >= 0")
+        if cap == 0:  # the counts alone (no array to write)
+            self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+        else:
+            rows = (out.row_env, getattr(out, k.field), out.reward)
+            self.handle.call(k.expand + "_scored", _lib.ptr(d), cap, _lib.ptr(offsets), *(_lib.ptr(a) for a in rows),
+                             ctypes.byref(mlp), PERSPECTIVES[perspective], _lib.ptr(values), self._s())
+        self._keep = (d, net)
+        return out._replace(cap=cap), values[:cap]
+
+    def scored_afterstates(self, net, dice=None, cap=None, perspective="white", out=None):
+        """afterstates() with the rows scored on the way (narde_afterstates_scored;
+        DESIGN.md section 15): net, a value_net.ValueMLP on the env's device, is
+        evaluated inside the fill pass and one float a row is written -- the
+        198-float rows are never made.  Returns (aft, values): aft an
+        Afterstates with feat and obs None; values (cap,) float32 = net's
+        value of each row, a terminal row's set to its outcome (reward, negated
+        in perspective "white" when black made the move) -- what
+        ValuePlayer.values() gives, ready for pick_afterstate().
+        cap / out as afterstates(): cap None makes the one synchronise; cap
+        given, or out = (an Afterstates of preallocated arrays, a (>= cap,)
+        float32 values tensor) -- or the Afterstates alone, values then
+        allocated --, none: graph-safe, and since the weights are
+        read through pointers a replay sees net's weights of that moment
+        (call net.pack() after changing them)."""
+        if self.full:
+            raise ValueError('scored_afterstates() is rules="ref2" only')
+        return self._scored_rows(_REF2_ROWS, net, dice, cap, perspective, out)
+
+    def scored_turn_afterstates(self, net, dice=None, cap=None, perspective="white", out=None):
+        """rules="full4": scored_afterstates() over turn_afterstates()' rows
+        (narde_turn_afterstates_scored, the overflow path included)."""
+        if not self.full:
+            raise ValueError('scored_turn_afterstates() is rules="full4" only')
+        return self._scored_rows(_FULL4_ROWS, net, dice, cap, perspective, out)
+
     def _pick_rows(self, k, aft, values, perspective, epsilon, tag, seed):
         """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""
         if perspective not in PERSPECTIVES:

@@ -378,6 +378,49 @@ int narde_turn_pick(narde_env *env, const int32_t *offsets, const int8_t *play, 
                     const float *value, int64_t ld_value, int perspective, const float *epsilon,
                     uint64_t seed, const int64_t *tag, int8_t *out_play, int32_t *row, void *stream);
 
+/* Afterstates scored by a built-in value MLP:
+ *   v(row) = g_out(b2 + sum_h w2[h] g_hid(b1[h] + sum_c feat[c] W1[h][c]))
+ * over the row's tesauro198 columns feat, which are never written: the fill
+ * pass evaluates the first layer as the env's own pre-activations plus the
+ * few columns in which the row differs from it, and stores one float a row.
+ * Every pointer of narde_value_mlp is device memory, read when the kernels
+ * run -- weights changed between two replays of a captured graph are seen by
+ * the second.  w1t is feature-major: w1t[c * ld_w1t + h] = W1[h][c]. */
+#define NARDE_VALUE_HIDDEN_MAX 128
+typedef struct narde_value_mlp {
+  const float *w1t;    /* f32[198][ld_w1t] */
+  int64_t ld_w1t;      /* >= hidden */
+  const float *b1;     /* f32[hidden] */
+  const float *w2;     /* f32[hidden] */
+  const float *b2;     /* f32[1] */
+  int32_t hidden;      /* 1 .. NARDE_VALUE_HIDDEN_MAX */
+  int32_t hidden_act;  /* 0 sigmoid, 1 tanh, 2 relu */
+  int32_t out_act;     /* 0 none, 1 sigmoid, 2 tanh */
+} narde_value_mlp;
+
+/* narde_afterstates with value f32[cap] in place of feat and obs: the same
+ * rows in the same order, offsets, cap rule and optional arrays (the count
+ * pass and the scan are that call's).  value[r] = v(row r) for a row of
+ * reward 0; a terminal row's is its outcome: reward as a float, negated when
+ * perspective is 1 (white's values) and the side that made the move is
+ * black; perspective 0: the mover's values (narde_afterstate_pick's two).
+ * Nothing at or past cap is touched.  Stream-ordered, allocates nothing, no
+ * synchronise, graph-capturable.  NARDE_EINVAL before any device call: NULL
+ * net, value or weights, hidden outside 1..NARDE_VALUE_HIDDEN_MAX, ld_w1t <
+ * hidden (or above 2^20), an unknown activation or perspective, a negative
+ * cap. */
+int narde_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                             int32_t *row_env, int16_t *codes, int8_t *reward,
+                             const narde_value_mlp *net, int perspective, float *value, void *stream);
+
+/* The same over narde_turn_afterstates' rows (FULL4), the overflow path
+ * included; that call's workspace rule holds (the handle's first call of
+ * either, outside capture). */
+int narde_turn_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                                  int32_t *row_env, int8_t *play, int8_t *reward,
+                                  const narde_value_mlp *net, int perspective, float *value,
+                                  void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry

@@ -23,6 +23,13 @@ trace, and the share of envs that take the overflow path (a level of more
 than 256 nodes: counted on the CPU by the test-only host build of the same
 rule functions, tests/hostcheck, on the env's states and dice).
 
+--scored: launches also runs the scored expansion
+(scored_afterstates: k_aft_fill_scored; full4: k_turn_fill_scored +
+k_turn_overflow_scored) under the 198 -> 80 -> 1 net, --reps times on the same
+env in the same trace, and table lists those kernels beside the plain fills;
+player times the fused ValuePlayer (a value_net.ValueMLP of the same weights)
+beside the unfused one.
+
 Algorithmic bytes: fill = rows x (792 + 4 + 4 + 1, + 96 with --obs) + B x
 (32 + 4) (full4: 8 B of play per row in place of 4 B of codes);
 k_tesauro198_rows = B x (32 + 792).
@@ -43,7 +50,17 @@ HBM_PEAK = 8.0e12
 KERNELS = ("k_aft_count", "k_aft_scan", "k_aft_fill", "k_aft_pick<unsigned int", "k_tesauro198_rows")
 KERNELS_FULL4 = ("k_turn_count", "k_turn_overflow<false", "k_aft_scan", "k_turn_fill", "k_turn_overflow<true",
                  "k_aft_pick<unsigned long", "k_aft_count", "k_aft_fill", "k_tesauro198_rows")
+KERNELS_SCORED = ("k_aft_fill_scored",)
+KERNELS_SCORED_FULL4 = ("k_turn_fill_scored", "k_turn_overflow_scored")
 FAST_FRONT = 256  # kernels_turn_afterstates.h kTurnFront
+
+
+def value_mlp(env):
+    """play_value_agent.make_net(0)'s weights as a value_net.ValueMLP."""
+    from gym_narde.value_net import ValueMLP
+    from play_value_agent import make_net
+
+    return ValueMLP.from_sequential(make_net(0, env.device)).pack()
 
 
 def setup(a):
@@ -91,9 +108,15 @@ def launches(a):
         ref2 = VecNardeEnv(B, device="cuda:0", seed=0)
         ref2.selfplay(40)
         aft2 = ref2.afterstates()
+    if a.scored:
+        net = value_mlp(env)
+        out_s = (aft._replace(feat=None, obs=None), torch.empty(rows, dtype=torch.float32, device=env.device))
+        scored = env.scored_turn_afterstates if env.full else env.scored_afterstates
     for rep in (a.warm, a.reps):
         for _ in range(rep):
             (env.turn_afterstates if env.full else env.afterstates)(out=aft)
+        for _ in range(rep if a.scored else 0):
+            scored(net, out=out_s)
         for _ in range(rep):
             (env.pick_turn if env.full else env.pick_afterstate)(aft, values)
         for _ in range(rep if ref2 is not None else 0):
@@ -103,6 +126,7 @@ def launches(a):
         torch.cuda.synchronize()
     cnt = (aft.offsets[1:] - aft.offsets[:-1]).float()
     res = dict(envs=B, rows=rows, rows_per_env=rows / B, max_rows=int(cnt.max()), obs=bool(a.obs), rules=a.rules,
+               scored=bool(a.scored), scored_bytes=rows * ((8 if env.full else 4) + 4 + 1 + 4) + B * (32 + 4),
                fill_bytes=rows * (792 + (8 if env.full else 4) + 4 + 1 + (96 if a.obs else 0)) + B * (32 + 4),
                tes_bytes=B * (32 + 792))
     if env.full:
@@ -120,6 +144,8 @@ def table(a):
     res = json.load(open(a.json))
     full = res.get("rules") == "full4"
     kernels = KERNELS_FULL4 if full else KERNELS
+    if res.get("scored"):
+        kernels = kernels + (KERNELS_SCORED_FULL4 if full else KERNELS_SCORED)
     mean = {}
     for r in csv.DictReader(open(a.stats)):
         for k in kernels:
@@ -128,6 +154,8 @@ def table(a):
     nbytes = {"k_aft_fill": res["fill_bytes"], "k_tesauro198_rows": res["tes_bytes"]}
     if full:
         nbytes = {"k_turn_fill": res["fill_bytes"], "k_aft_fill": res["ref2_fill_bytes"], "k_tesauro198_rows": res["tes_bytes"]}
+    if res.get("scored"):
+        nbytes["k_turn_fill_scored" if full else "k_aft_fill_scored"] = res["scored_bytes"]
     print(f"B = {res['envs']}, {res['rows']} rows ({res['rows_per_env']:.2f} per env, max {res['max_rows']}), "
           f"obs {'on' if res['obs'] else 'off'}" +
           (f", rules full4; {100 * res['overflow_share']:.4f} % of envs on the overflow path (largest level "
@@ -152,19 +180,25 @@ def player(a):
     from gym_narde.value_play import ValuePlayer
     from play_value_agent import make_net
 
-    p = ValuePlayer(env, make_net(0, env.device))
-    for _ in range(a.warm):
-        p.step()
-    torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    rows = 0
-    for _ in range(a.reps):
-        rows += p.step()[5].cap
-    e.record()
-    torch.cuda.synchronize()
-    print(json.dumps(dict(envs=a.envs, plies=a.reps, ms_per_ply=s.elapsed_time(e) / a.reps,
-                          rows_per_ply=rows / a.reps)))
+    def run(p):
+        for _ in range(a.warm):
+            p.step()
+        torch.cuda.synchronize()
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        rows = 0
+        for _ in range(a.reps):
+            rows += p.step()[5].cap
+        e.record()
+        torch.cuda.synchronize()
+        return dict(ms_per_ply=s.elapsed_time(e) / a.reps, rows_per_ply=rows / a.reps)
+
+    res = dict(envs=a.envs, plies=a.reps, rules=a.rules, **run(ValuePlayer(env, make_net(0, env.device))))
+    if a.scored:  # a fresh env at the same point of the same games
+        env.close()
+        torch, env, _ = setup(a)
+        res["fused"] = run(ValuePlayer(env, value_mlp(env)))
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
@@ -175,6 +209,7 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--obs", action="store_true")
     ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
+    ap.add_argument("--scored", action="store_true")
     ap.add_argument("--json", default=None)
     ap.add_argument("--stats", default=None)
     a = ap.parse_args()
