@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A TD-Gammon-style value agent playing itself on the GPU: a fixed-seed
-198 -> 80 -> 1 MLP (Tesauro's shape; untrained here -- load your own weights
-with --weights) scores the afterstates of every env's roll and both sides
+198 -> 80 -> 1 MLP (Tesauro's shape; untrained here -- load weights with
+--weights, such as examples/train_value_agent.py saves) scores the afterstates of every env's roll and both sides
 play the best one for them (white the largest value, black the smallest:
 the README's reward is "+1 if WHITE wins").  Everything per ply runs on the
 device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step
@@ -40,7 +40,12 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
     env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
     net = make_net(seed, env.device)
     if weights:
-        net.load_state_dict(torch.load(weights, map_location=env.device))
+        sd = torch.load(weights, map_location=env.device)
+        if "l1.weight" in sd:  # a value_net.ValueMLP's (examples/train_value_agent.py): the same two layers
+            sd = {k.replace("l1.", "0.").replace("l2.", "2."): v for k, v in sd.items()}
+            hidden = sd["0.weight"].shape[0]
+            net[0], net[2] = torch.nn.Linear(198, hidden).to(env.device), torch.nn.Linear(hidden, 1).to(env.device)
+        net.load_state_dict(sd)
     if fused:
         from gym_narde.value_net import ValueMLP
 

@@ -1,0 +1,65 @@
+#!/usr/bin/env python3
+"""TD(lambda) self-play on the GPU: trains the 198 -> H -> 1 value network
+that examples/play_value_agent.py plays with (TD-Gammon's recipe).  Every ply
+of every env: the eligibility traces take the gradient of v(s), both sides
+play the afterstate that is best for them (epsilon-greedy), and the weights
+move by alpha x sum_e delta_e x trace_e -- gym_narde.td.TDLambdaLearner, all
+of it on the device.  The output is tanh by default:
+outcomes are +-1 and +-2 (white's points, negative when black wins), which a
+sigmoid cannot reach.
+
+  python examples/train_value_agent.py [--envs B] [--plies N] [--hidden H] [--alpha A] [--lam L] [--epsilon E]
+                                       [--rules ref2|full4] [--out-act none|sigmoid|tanh] [--seed S] [--out FILE]
+
+Play the result:  python examples/play_value_agent.py --weights FILE --fused
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "gym-narde_amd"))
+
+
+def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rules="ref2", out_act="tanh", seed=0,
+         out="value_agent.pt", device="cuda", report=10):
+    import torch
+
+    from gym_narde.td import TDLambdaLearner
+    from gym_narde.value_net import ValueMLP
+    from gym_narde.vector import VecNardeEnv
+
+    env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
+    torch.manual_seed(seed)
+    net = ValueMLP(hidden, "sigmoid", out_act).to(env.device)
+    learner = TDLambdaLearner(env, net, alpha=alpha, lam=lam, epsilon=epsilon, seed=seed)
+    print(f"{envs} envs, hidden {hidden}, out {out_act}: learner memory {learner.memory_bytes() / 1e6:.1f} MB")
+    every = max(1, plies // max(1, report))
+    err = torch.zeros((), device=env.device)
+    for ply in range(plies):
+        delta = learner.step()[-1]
+        err += delta.abs().mean()
+        if (ply + 1) % every == 0 or ply + 1 == plies:
+            n = (ply % every) + 1
+            ep = int(env.stats().sum(0)[0])
+            print(f"ply {ply + 1}: mean |delta| {float(err) / n:.4f}, {ep} games finished")
+            err.zero_()
+    torch.save(net.state_dict(), out)
+    print(f"saved {out}")
+    env.close()
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--plies", type=int, default=2000)
+    ap.add_argument("--hidden", type=int, default=80)
+    ap.add_argument("--alpha", type=float, default=1e-4)
+    ap.add_argument("--lam", type=float, default=0.7)
+    ap.add_argument("--epsilon", type=float, default=0.1)
+    ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
+    ap.add_argument("--out-act", choices=("none", "sigmoid", "tanh"), default="tanh")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default="value_agent.pt")
+    a = ap.parse_args()
+    main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out)

@@ -25,6 +25,8 @@
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
 //                       (k_turn_count, k_turn_fill, k_turn_overflow, and the
 //                       scored fills)
+//   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
+//                       errors, the slab sums and the weight update
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip);
 // host_common.h: the host helpers the two share.
@@ -52,6 +54,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_rows.h"
 #include "kernels_afterstates.h"
 #include "kernels_turn_afterstates.h"
+#include "kernels_td.h"
 
 namespace {
 
@@ -195,6 +198,31 @@ int check_value_net(const narde_value_mlp* net, int perspective, float* value, V
     return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
   vn = ValNet{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act, net->out_act,
               perspective, value};
+  return NARDE_OK;
+}
+
+// narde_value_td_trace's and narde_value_td_apply's checks of the net and the
+// trace rows, and the kernels' view of the net
+static_assert(kTdSlab == NARDE_TD_SLAB, "narde.h and narde_rules.h state the same slab");
+int check_td(const narde_env* e, const narde_value_mlp_train* net, const float* trace, int64_t ld_trace,
+             const float* v, const uint8_t* black, TdNet& tn) {
+  if (!e || !net || !trace || !v || !black) return fail(NARDE_EINVAL, "NULL argument");
+  if (!net->w1t || !net->b1 || !net->w2 || !net->b2) return fail(NARDE_EINVAL, "the net has a NULL weight array");
+  if (net->hidden < 1 || net->hidden > NARDE_VALUE_HIDDEN_MAX)
+    return fail(NARDE_EINVAL, "hidden %d outside 1..%d", (int)net->hidden, NARDE_VALUE_HIDDEN_MAX);
+  if (net->ld_w1t < net->hidden || net->ld_w1t > kValLdMax)
+    return fail(NARDE_EINVAL, "ld_w1t %lld outside hidden %d .. %lld", (long long)net->ld_w1t, (int)net->hidden,
+                (long long)kValLdMax);
+  if (net->w1 && net->ld_w1 < 198) return fail(NARDE_EINVAL, "ld_w1 %lld below 198", (long long)net->ld_w1);
+  if (net->hidden_act < 0 || net->hidden_act > 2 || net->out_act < 0 || net->out_act > 2)
+    return fail(NARDE_EINVAL, "activations: hidden 0 sigmoid, 1 tanh, 2 relu; out 0 none, 1 sigmoid, 2 tanh");
+  const int64_t P = td_row_floats(net->hidden);
+  if (ld_trace < P || (ld_trace & 3))
+    return fail(NARDE_EINVAL, "ld_trace %lld: a multiple of 4, at least 200 x hidden + 1 = %lld", (long long)ld_trace,
+                (long long)P);
+  if (!aligned16(trace)) return fail(NARDE_EINVAL, "trace must be 16-B aligned");
+  tn = TdNet{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->w1, net->ld_w1, net->hidden, net->hidden_act,
+             net->out_act};
   return NARDE_OK;
 }
 
@@ -721,6 +749,48 @@ int narde_turn_afterstates_scored(narde_env* e, const uint8_t* dice, int64_t cap
   if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
   DeviceGuard dg(e->device);
   return expand_turns(e, dice, cap, offsets, row_env, play, nullptr, nullptr, reward, &vn, (hipStream_t)stream);
+}
+
+int narde_value_td_trace(narde_env* e, const narde_value_mlp_train* net, float decay, float* trace, int64_t ld_trace,
+                         float* v, uint8_t* black, void* stream) {
+  TdNet tn;
+  if (const int rc = check_td(e, net, trace, ld_trace, v, black, tn)) return rc;
+  DeviceGuard dg(e->device);
+  k_td_trace<<<(unsigned)e->n, kTdBlock, 0, (hipStream_t)stream>>>(e->pl, (int)e->n, tn, decay, trace, ld_trace, v,
+                                                                    black);
+  return check_launch("k_td_trace");
+}
+
+int narde_value_td_apply(narde_env* e, const narde_value_mlp_train* net, float* trace, int64_t ld_trace, const float* v,
+                         const uint8_t* black, const int32_t* reward, const uint8_t* terminated,
+                         const uint8_t* truncated, float alpha, float gamma, int perspective, float* scratch,
+                         int64_t scratch_floats, float* delta, void* stream) {
+  TdNet tn;
+  if (const int rc = check_td(e, net, trace, ld_trace, v, black, tn)) return rc;
+  if (!reward || !terminated || !truncated || !scratch) return fail(NARDE_EINVAL, "NULL argument");
+  if (perspective != 1) return fail(NARDE_EINVAL, "perspective must be 1 (white's values)");
+  const int64_t need = NARDE_TD_SCRATCH_FLOATS(e->n, tn.hidden);
+  if (scratch_floats < need)
+    return fail(NARDE_EINVAL, "scratch_floats %lld below NARDE_TD_SCRATCH_FLOATS = %lld", (long long)scratch_floats,
+                (long long)need);
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  const int n = (int)e->n, waves = kTdBlock / 64;
+  const int slabs = (n + kTdSlab - 1) / kTdSlab;
+  const int64_t ld_part = td_row_floats(tn.hidden) + 3;  // (P = 1 mod 4: whole float4 pieces)
+  float* dl = scratch;
+  float* part = scratch + (e->n + 3) / 4 * 4;
+  k_td_delta<<<(unsigned)((n + waves - 1) / waves), kTdBlock, 0, st>>>(e->pl, n, tn, v, black, reward, terminated,
+                                                                        truncated, gamma, dl, delta);
+  if (const int rc = check_launch("k_td_delta")) return rc;
+  const unsigned pieces = (unsigned)((kTdCols / 4) * tn.hidden + 1);  // the float4 pieces and b2's float
+  k_td_partial<<<dim3((pieces + kTdBlock - 1) / kTdBlock, (unsigned)slabs), kTdBlock, 0, st>>>(
+      n, tn.hidden, trace, ld_trace, dl, terminated, truncated, part, ld_part);
+  if (const int rc = check_launch("k_td_partial")) return rc;
+  k_td_update<<<(unsigned)((td_row_floats(tn.hidden) + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part,
+                                                                                                   ld_part, slabs);
+  return check_launch("k_td_update");
 }
 
 int narde_turn_pick(narde_env* e, const int32_t* offsets, const int8_t* play, int64_t cap, const float* value,

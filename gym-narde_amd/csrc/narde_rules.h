@@ -2220,6 +2220,107 @@ NARDE_FN float val_outcome(int reward, uint32_t black, int perspective) {
   return perspective == 1 && black ? -r : r;
 }
 
+// ------------------------------------------------- TD(lambda)
+// The gradient of v by the weights, from what the forward above leaves: with
+// a_h = g_hid(z_h), y = b2 + sum_h w2[h] a_h, v = g_out(y) and go = g_out'(y),
+//   dv/db2 = go, dv/dw2[h] = go a_h, d_h = go w2[h] g_hid'(z_h) = dv/db1[h],
+//   dv/dW1[h][c] = d_h x_c -- non-zero on the record's own columns only.
+// A trace row holds them as T[c hidden + h] for c < 198, then b1, w2, b2:
+// kTdCols "columns" of hidden floats and one float.  The kernels
+// (kernels_td.h) and the host check (tests/hostcheck/hostcheck_td.cpp) run
+// these same functions.
+constexpr int kTdCols = 200;      // 198 feature columns, b1, w2
+constexpr int kTdColB1 = 198;
+constexpr int kTdColW2 = 199;
+constexpr int kTdMaskWords = 7;   // 198 column bits
+constexpr int kTdSlab = 64;       // envs a partial row of the apply pass sums
+
+NARDE_FN int64_t td_row_floats(int hidden) { return (int64_t)kTdCols * hidden + 1; }
+
+NARDE_FN float val_hid_act(float z, int act) {
+  return act == 0 ? val_sigmoid(z) : (act == 1 ? val_tanh(z) : (z > 0.0f ? z : 0.0f));
+}
+// g_hid'(z) from a = g_hid(z), g_out'(y) from v = g_out(y)
+NARDE_FN float val_hid_slope(float z, float a, int act) {
+  return act == 0 ? a * (1.0f - a) : (act == 1 ? 1.0f - a * a : (z > 0.0f ? 1.0f : 0.0f));
+}
+NARDE_FN float val_out_slope(float v, int act) { return act == 0 ? 1.0f : (act == 1 ? v * (1.0f - v) : 1.0f - v * v); }
+
+// val_lane_part that keeps the lane's activations: a[i] = g_hid(z[i])
+template <int NU>
+NARDE_FN float val_lane_acts(const float (&z)[kValUnits], const float (&w2t)[kValUnits], int act,
+                             float (&a)[kValUnits]) {
+  float part = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NU; ++i) {
+    a[i] = val_hid_act(z[i], act);
+    part += w2t[i] * a[i];
+  }
+  return part;
+}
+// a unit's two pieces: ga = dv/dw2[h], d = d_h
+NARDE_FN void td_unit_grad(float go, float w2, float z, float a, int act, float& ga, float& d) {
+  ga = go * a;
+  d = go * w2 * val_hid_slope(z, a, act);
+}
+
+// A record's columns for the trace pass: bit c of mask = column c is
+// non-zero, its value xv[the number of set bits below c] (val_root_list's
+// order: ascending columns); pre[w] = the set bits of the words below w.
+struct TdCols {
+  uint32_t mask[kTdMaskWords], pre[kTdMaskWords];
+  float xv[kValRootSlots];
+};
+NARDE_FN void td_cols_prefix(TdCols& C) {
+  uint32_t n = 0;
+  for (int w = 0; w < kTdMaskWords; ++w) {
+    C.pre[w] = n;
+    n += (uint32_t)__builtin_popcount(C.mask[w]);
+  }
+}
+// serially (the kernel places the items by a wave prefix sum instead)
+NARDE_FN void td_cols_of(const uint4& a, const uint4& b, TdCols& C) {
+  for (int w = 0; w < kTdMaskWords; ++w) C.mask[w] = 0u;
+  int k = 0;
+  for (int item = 0; item < kValRootItems; ++item) {
+    int col[4];
+    float val[4];
+    const int c = tes_item_nonzero(a, b, item, col, val);
+    for (int j = 0; j < c; ++j)
+      if (k < kValRootSlots) {
+        C.mask[col[j] >> 5] |= 1u << (col[j] & 31);
+        C.xv[k++] = val[j];
+      }
+  }
+  td_cols_prefix(C);
+}
+
+// element (column c <= kTdCols, unit h) of the gradient row; false: it is
+// zero (a feature column the record does not hold).  d, ga: the units'
+// pieces (td_unit_grad), by unit.
+NARDE_FN bool td_grad_at(int c, int h, const TdCols& C, const float* d, const float* ga, float go, float& g) {
+  if (c < kTdColB1) {
+    const uint32_t word = C.mask[c >> 5], bit = 1u << (c & 31);
+    if (!(word & bit)) return false;
+    g = d[h] * C.xv[C.pre[c >> 5] + (uint32_t)__builtin_popcount(word & (bit - 1u))];
+    return true;
+  }
+  g = c == kTdColB1 ? d[h] : (c == kTdColW2 ? ga[h] : go);
+  return true;
+}
+// the trace element's update, trace = decay trace + gradient; decay 0
+// never reads (old is then any value, never used)
+NARDE_FN float td_trace_at(float decay, float old, bool hit, float g) {
+  if (decay == 0.0f) return hit ? g : 0.0f;
+  return hit ? fmaf(decay, old, g) : decay * old;
+}
+// an env's TD target and error
+NARDE_FN float td_delta(bool terminated, bool truncated, int reward, uint32_t black, float gamma, float v_next,
+                        float v) {
+  const float target = terminated ? val_outcome(reward, black, 1) : (truncated ? v : gamma * v_next);
+  return target - v;
+}
+
 // ------------------------------------------------------------- Philox4x32-10
 NARDE_FN void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                             uint32_t k1, uint32_t out[4]) {

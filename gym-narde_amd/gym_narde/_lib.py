@@ -13,12 +13,19 @@ LIB_PATH = os.environ.get("NARDE_LIB", os.path.join(HERE, "libnarde.so"))
 OK = 0
 OFF = 24
 MAX_MOVES = 64
+TD_SLAB = 64  # NARDE_TD_SLAB
 TOTAL_ROWS = 64  # NARDE_TOTAL_ROWS
 
 
 def wg_rows(num_envs):
     """NARDE_WG_ROWS: rows of narde_rollout_timed's per-workgroup totals."""
     return (int(num_envs) + 255) // 256
+
+
+def td_scratch_floats(num_envs, hidden):
+    """NARDE_TD_SCRATCH_FLOATS: narde_value_td_apply's scratch."""
+    b = int(num_envs)
+    return (b + 3) // 4 * 4 + (b + TD_SLAB - 1) // TD_SLAB * (200 * int(hidden) + 4)
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
 
@@ -34,6 +41,12 @@ class ValueMlp(ctypes.Structure):
     """narde_value_mlp: device pointers of a 198 -> hidden -> 1 value net."""
     _fields_ = [("w1t", _vp), ("ld_w1t", _i64), ("b1", _vp), ("w2", _vp), ("b2", _vp),
                 ("hidden", ctypes.c_int32), ("hidden_act", ctypes.c_int32), ("out_act", ctypes.c_int32)]
+
+
+class ValueMlpTrain(ctypes.Structure):
+    """narde_value_mlp_train: ValueMlp's fields, writable, and the optional
+    row-major mirror of the first layer."""
+    _fields_ = ValueMlp._fields_ + [("w1", _vp), ("ld_w1", _i64)]
 
 
 # name -> (restype, argtypes); mirrors include/narde.h one to one
@@ -80,6 +93,9 @@ SIGNATURES = {
     "narde_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp]),
     "narde_turn_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
                                              _vp]),
+    "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
+    "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                    ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

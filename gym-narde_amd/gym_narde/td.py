@@ -1,0 +1,112 @@
+"""TD(lambda) self-play for a value_net.ValueMLP, on the device (DESIGN.md
+section 16): the learner the value-greedy path (value_play.ValuePlayer) was
+missing.
+
+Every ply, for all B envs at once:
+    trace  <- gamma lam trace + grad_theta v(s)         narde_value_td_trace
+    a ply of value-greedy play (epsilon-greedy with epsilon)   ValuePlayer.step
+    delta  <- target - v(s),  theta <- theta + alpha sum_e delta_e trace_e
+                                                        narde_value_td_apply
+with target = the outcome at a terminal step, v(s) at a truncated one (no
+successor under autoreset) and gamma v(s') otherwise.  Values are white's
+(the README's reward, +1 / +2 if WHITE wins, negated for black).
+
+The kernels train net._w1t (what the scored expansions read) and the module's
+own parameters in place, l1.weight as the mirror of _w1t: net(feat),
+state_dict() and scored_afterstates(net) agree after every update and no
+pack() is needed.
+"""
+import ctypes
+
+from . import _lib
+from .value_net import HIDDEN_ACTS, OUT_ACTS
+from .value_play import ValuePlayer
+
+
+class TDLambdaLearner:
+    """env: a VecNardeEnv (either rule set) with autoreset; net: a ValueMLP on
+    its device.  alpha: step size; lam: the trace decay; gamma: the discount;
+    epsilon: the explore probability of the play (None: greedy); cap: the
+    rows a ply's expansion holds (ValuePlayer's: with it a step makes no
+    synchronise)."""
+
+    def __init__(self, env, net, alpha, lam, gamma=1.0, epsilon=None, seed=0, cap=None):
+        t = env.torch
+        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+            raise TypeError("TDLambdaLearner needs a gym_narde.value_net.ValueMLP")
+        if not env.autoreset:
+            raise ValueError("TDLambdaLearner needs an env with autoreset=True")
+        if net.l1.weight.device != env.device:
+            raise ValueError(f"the net is on {net.l1.weight.device}, the env on {env.device}")
+        if not 0.0 <= float(lam) <= 1.0:
+            raise ValueError("lam must be in [0, 1]")
+        self.env, self.net = env, net
+        self.alpha, self.lam, self.gamma, self.seed = float(alpha), float(lam), float(gamma), int(seed)
+        B, H = env.num_envs, net.hidden
+        self.row_floats = 200 * H + 1
+        self.ld_trace = (self.row_floats + 3) // 4 * 4
+        need = B * self.ld_trace * 4
+        free = t.cuda.mem_get_info(env.device)[0]
+        if need > free:
+            raise ValueError(f"{B} envs x {self.ld_trace} trace floats = {need / 1e6:.0f} MB exceed the device's free "
+                             f"memory ({free / 1e6:.0f} MB): use fewer envs or a smaller hidden layer")
+        z = dict(device=env.device)
+        self.trace = t.zeros((B, self.ld_trace), dtype=t.float32, **z)
+        self.v = t.zeros(B, dtype=t.float32, **z)
+        self.black = t.zeros(B, dtype=t.uint8, **z)
+        self.delta = t.zeros(B, dtype=t.float32, **z)
+        self.scratch = t.empty(_lib.td_scratch_floats(B, H), dtype=t.float32, **z)
+        self.player = ValuePlayer(env, net, perspective="white", fused=True, cap=cap)
+        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
+        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
+        self._mlp = self.struct()
+
+    def struct(self):
+        """The ctypes narde_value_mlp_train over the net's live tensors."""
+        net, t = self.net, self.env.torch
+        net.struct()  # packs _w1t on first use, checks the parameters
+        w = net.l1.weight
+        if w.dtype != t.float32 or not w.is_contiguous():
+            raise ValueError("the learner needs a contiguous float32 l1.weight")
+        return _lib.ValueMlpTrain(net._w1t.data_ptr(), net.hidden, net.l1.bias.data_ptr(), net.l2.weight.data_ptr(),
+                                  net.l2.bias.data_ptr(), net.hidden, HIDDEN_ACTS[net.hidden_act],
+                                  OUT_ACTS[net.out_act], w.data_ptr(), w.stride(0))
+
+    def trace_pass(self, decay=None):
+        """v, black and the traces from the envs' records as they stand."""
+        decay = self.gamma * self.lam if decay is None else float(decay)
+        self.env.handle.call("narde_value_td_trace", ctypes.byref(self._mlp), decay, _lib.ptr(self.trace),
+                             self.ld_trace, _lib.ptr(self.v), _lib.ptr(self.black), self.env._s())
+
+    def apply_pass(self, reward, terminated, truncated):
+        """The update after the step (its reward, terminated, truncated)."""
+        self.env.handle.call("narde_value_td_apply", ctypes.byref(self._mlp), _lib.ptr(self.trace), self.ld_trace,
+                             _lib.ptr(self.v), _lib.ptr(self.black), _lib.ptr(reward), _lib.ptr(terminated),
+                             _lib.ptr(truncated), self.alpha, self.gamma, 1, _lib.ptr(self.scratch),
+                             self.scratch.numel(), _lib.ptr(self.delta), self.env._s())
+
+    def step(self):
+        """One ply of self-play and its update.  Returns ValuePlayer.step's
+        tuple plus delta (B,) float32, the ply's TD errors."""
+        self.trace_pass()
+        if self._eps is None:
+            out = self.player.step()
+        else:
+            out = self.player.step(epsilon=self._eps, tag=self._tag, seed=self.seed)
+            self._tag += 1
+        self.apply_pass(out[1], out[2], out[3])
+        return out + (self.delta,)
+
+    def traces(self):
+        """The traces shaped like the module's parameters with a leading B
+        (views of the learner's buffer)."""
+        B, H = self.env.num_envs, self.net.hidden
+        tr = self.trace
+        return {"l1.weight": tr[:, :198 * H].reshape(B, 198, H).transpose(1, 2),
+                "l1.bias": tr[:, 198 * H:199 * H],
+                "l2.weight": tr[:, 199 * H:200 * H].reshape(B, 1, H),
+                "l2.bias": tr[:, 200 * H:200 * H + 1]}
+
+    def memory_bytes(self):
+        """Device memory the learner owns."""
+        return sum(x.numel() * x.element_size() for x in (self.trace, self.v, self.black, self.delta, self.scratch))

@@ -421,6 +421,73 @@ int narde_turn_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t c
                                   const narde_value_mlp *net, int perspective, float *value,
                                   void *stream);
 
+/* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
+ * section 16).  narde_value_mlp_train: narde_value_mlp's fields, the weights
+ * writable, and an optional mirror of the first layer: w1, row-major
+ * [hidden][ld_w1] (ld_w1 >= 198), w1[h * ld_w1 + c] = w1t[c * ld_w1t + h] --
+ * a torch Linear(198, hidden).weight; NULL: none.  Every update writes w1t
+ * and the mirror the same bits, so the scored calls above see the new
+ * weights at their next launch.
+ *
+ * A trace row is P = 200 * hidden + 1 floats: T[c * hidden + h] = the trace
+ * of W1[h][c] for column c < 198 (dense, whatever ld_w1t), then b1's at
+ * 198 * hidden, w2's at 199 * hidden, b2's at 200 * hidden.  trace
+ * f32[B][ld_trace], 16-B aligned, ld_trace >= P and a multiple of 4; floats
+ * past P of a row are never touched. */
+typedef struct narde_value_mlp_train {
+  float *w1t;          /* f32[198][ld_w1t] */
+  int64_t ld_w1t;      /* >= hidden */
+  float *b1;           /* f32[hidden] */
+  float *w2;           /* f32[hidden] */
+  float *b2;           /* f32[1] */
+  int32_t hidden;      /* 1 .. NARDE_VALUE_HIDDEN_MAX */
+  int32_t hidden_act;  /* 0 sigmoid, 1 tanh, 2 relu */
+  int32_t out_act;     /* 0 none, 1 sigmoid, 2 tanh */
+  float *w1;           /* f32[hidden][ld_w1] or NULL */
+  int64_t ld_w1;       /* >= 198 when w1 is given */
+} narde_value_mlp_train;
+
+/* For every env e, from its record as it stands: v[e] = v(s_e) (white's
+ * value, the net's forward), black[e] (u8) = 1 when black is to move, and
+ *   trace[e] = decay * trace[e] + grad_theta v(s_e).
+ * decay == 0 overwrites the row without reading it (uninitialised memory is
+ * fine).  Stream-ordered, allocates nothing, no synchronise,
+ * graph-capturable.  NARDE_EINVAL before any device call: a NULL env, net,
+ * trace, v, black or weight array, hidden outside
+ * 1..NARDE_VALUE_HIDDEN_MAX, ld_w1t < hidden (or above 2^20), ld_w1 < 198
+ * with a mirror, an unknown activation, ld_trace < P or not a multiple of
+ * 4, trace not 16-B aligned. */
+int narde_value_td_trace(narde_env *env, const narde_value_mlp_train *net, float decay, float *trace,
+                         int64_t ld_trace, float *v, uint8_t *black, void *stream);
+
+/* The update after the step that followed narde_value_td_trace; v and black
+ * are that call's, reward i32[B], terminated and truncated u8[B] the
+ * step's.  Per env
+ *   target = the outcome -- reward, negated when black[e] -- if terminated,
+ *            v[e] if truncated (delta 0: under autoreset the successor is
+ *            gone), else gamma * v(s'_e) from the env's record as it stands,
+ *            under the weights before this update;
+ *   delta_e = target - v[e], written to delta f32[B] if not NULL;
+ * then theta += alpha * sum_e delta_e * trace[e] into w1t, b1, w2, b2 and
+ * the mirror, and the trace rows of terminated or truncated envs are zeroed.
+ * The sum has one order -- partial rows over slabs of NARDE_TD_SLAB envs in
+ * env order, kept in scratch, then the partial rows in slab order -- and no
+ * float atomics: the same inputs give the same bits.  scratch: device
+ * memory, 16-B aligned, scratch_floats >= NARDE_TD_SCRATCH_FLOATS(B, hidden).
+ * perspective must be 1 (white's values): the mover's have no successor
+ * sign under a bounded output.  Stream-ordered, allocates nothing, no
+ * synchronise, graph-capturable.  NARDE_EINVAL before any device call:
+ * narde_value_td_trace's cases, a NULL reward, terminated, truncated or
+ * scratch, perspective != 1, scratch too small or misaligned. */
+#define NARDE_TD_SLAB 64
+#define NARDE_TD_SCRATCH_FLOATS(B, hidden) \
+  ((((int64_t)(B) + 3) / 4) * 4 + (((int64_t)(B) + NARDE_TD_SLAB - 1) / NARDE_TD_SLAB) * (200 * (int64_t)(hidden) + 4))
+int narde_value_td_apply(narde_env *env, const narde_value_mlp_train *net, float *trace, int64_t ld_trace,
+                         const float *v, const uint8_t *black, const int32_t *reward,
+                         const uint8_t *terminated, const uint8_t *truncated, float alpha, float gamma,
+                         int perspective, float *scratch, int64_t scratch_floats, float *delta,
+                         void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry
