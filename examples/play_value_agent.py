@@ -9,9 +9,12 @@ device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step
 turn_afterstates -> net -> pick_turn -> step).  --fused: the net becomes a
 value_net.ValueMLP and the rows are scored inside the expansion
 (scored_afterstates / scored_turn_afterstates: one float a row, the 198-float
-rows never made).
+rows never made).  --depth 2 (ref2, implies --fused): a two-ply search --
+every afterstate is valued by the expectation, over the opponent's rolls, of
+the opponent's best reply under the same net (lookahead_afterstates; --plies
+is already the number of plies played).
 
-  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused]
+  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2]
 """
 import argparse
 import os
@@ -31,7 +34,7 @@ def make_net(seed, device):
     return net.to(device).eval()
 
 
-def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False):
+def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False, depth=1):
     import torch
 
     from gym_narde.value_play import ValuePlayer
@@ -46,11 +49,11 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
             hidden = sd["0.weight"].shape[0]
             net[0], net[2] = torch.nn.Linear(198, hidden).to(env.device), torch.nn.Linear(hidden, 1).to(env.device)
         net.load_state_dict(sd)
-    if fused:
+    if fused or depth == 2:
         from gym_narde.value_net import ValueMLP
 
         net = ValueMLP.from_sequential(net)
-    player = ValuePlayer(env, net, perspective="white")
+    player = ValuePlayer(env, net, perspective="white", plies=depth)
     eps = torch.tensor(epsilon, dtype=torch.float32, device=env.device) if epsilon > 0 else None
     rows = 0
     for ply in range(plies):
@@ -73,5 +76,6 @@ if __name__ == "__main__":
     ap.add_argument("--weights", default=None)
     ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
     ap.add_argument("--fused", action="store_true")
+    ap.add_argument("--depth", type=int, choices=(1, 2), default=1)
     a = ap.parse_args()
-    main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused)
+    main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused, depth=a.depth)

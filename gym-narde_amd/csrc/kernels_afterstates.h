@@ -18,6 +18,8 @@ namespace {
 //      with the earlier lanes of its own chunk (v_readlane);
 //   3. a ballot of the survivors and a popcount below the lane give each its
 //      row: rows are in enumeration order with no atomics.
+// aft_entries is step 1, aft_chunks steps 2 and 3; the position is an env's
+// record here and a row's in the lookahead pass (kernels_lookahead.h).
 // The count pass stops there (the env's count -> offsets[e + 1], then
 // k_aft_scan); the fill pass also builds each survivor's afterstate, writes
 // its narrow outputs from the lane, and stages the 198-float rows 8 at a
@@ -48,19 +50,11 @@ struct alignas(16) AftScan {  // per wave, both passes
   uint32_t word[64];                // the entries' kPlayStep words
 };
 
-// env e's rows (all lanes of the wave call it with the same e); returns the
-// number of rows.  kFill: write them from row a.offsets[e] on, below a.cap.
-// kScore (a fill with a.feat NULL): the rows' values under vn as well
-// (kernels_rows.h "the scored rows"; VS the wave's lists).
-template <bool kFill, bool kScore = false>
-__device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftStage* S, const ValNet* vn = nullptr,
-                                       ValStage* VS = nullptr) {
-  const int lane = threadIdx.x & 63;
-  const Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
-  int d0, d1;
-  if (!play_dice(s, a.g, e, a.dice, d0, d1)) return 0;  // wave-uniform
-  Legal l;
-  legal2(s, d0, d1, l);
+// Step 1 for the position s and the roll (d0, d1), l = legal2(s, d0, d1): the
+// entries' words and the prefix sums of their play counts into L; returns
+// the number of plays (scalar).  All lanes of the wave call it with the same
+// position: an env's record (aft_env) or a row's (kernels_lookahead.h).
+__device__ __forceinline__ int aft_entries(const Side& s, int d0, int d1, const Legal& l, AftScan& L, int lane) {
   const int n1 = l.count;
   {
     const int k = lane >= 24 ? 1 : 0, p = (lane - 24 * k) & 31;
@@ -75,13 +69,16 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
     L.word[lane] = word;
   }
   wave_lds_handoff();
-  const int total = __builtin_amdgcn_readfirstlane((int)L.incl[63]);  // <= kAftMaxPlays; scalar: uniform loops
-  const int64_t row0 = kFill ? (int64_t)a.offsets[e] : 0;
-  ValRoot vr;
-  if constexpr (kScore) {
-    if (total == 0) return 0;  // wave-uniform: no play, nothing to score
-    val_root(vr, *vn, *VS, a.pl.p0[e], a.pl.p1[e], lane);
-  }
+  return __builtin_amdgcn_readfirstlane((int)L.incl[63]);  // <= kAftMaxPlays; scalar: uniform loops
+}
+
+// Steps 2 and 3 over the `total` plays aft_entries left in L, 64 a chunk:
+// chunk(nkept, keep, rank, nnew, y) once per chunk, by every lane -- nkept
+// rows kept before the chunk, the lane's play y kept or not, its rank among
+// the chunk's nnew kept.  Returns the number of rows.
+template <typename F>
+__device__ __forceinline__ int aft_chunks(const Legal& l, int total, AftScan& L, int lane, F&& chunk) {
+  const int n1 = l.count;
   int nkept = 0;
   for (int c0 = 0; c0 < total; c0 += 64) {
     const bool act = c0 + lane < total;
@@ -105,6 +102,44 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
     const int rank = wave_keep_rank(keep, lane, nnew);
     if (keep) L.keys[nkept + rank] = key;
     if (lane < 3) L.keys[nkept + nnew + lane] = kAftNoKey;
+    chunk(nkept, keep, rank, nnew, y);
+    nkept += nnew;
+    wave_lds_handoff();  // the keys, to the next chunk
+  }
+  return nkept;
+}
+
+// What the record fill (kernels_lookahead.h) writes besides the narrow
+// outputs: row R's record after the step at rec[2 R], rec[2 R + 1] -- its
+// ply-counter word replaced by the step's reward, which the lookahead pass
+// reads as "terminal" -- and a terminal row's outcome in white's perspective.
+struct AftRec {
+  uint4* __restrict__ rec;    // [cap][2]
+  float* __restrict__ value;  // [cap]
+};
+
+// env e's rows (all lanes of the wave call it with the same e); returns the
+// number of rows.  kFill: write them from row a.offsets[e] on, below a.cap.
+// kScore (a fill with a.feat NULL): the rows' values under vn as well
+// (kernels_rows.h "the scored rows"; VS the wave's lists).  kRec (a fill
+// with a.feat NULL): the rows' records to *ar as well.
+template <bool kFill, bool kScore = false, bool kRec = false>
+__device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftStage* S, const ValNet* vn = nullptr,
+                                       ValStage* VS = nullptr, const AftRec* ar = nullptr) {
+  const int lane = threadIdx.x & 63;
+  const Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
+  int d0, d1;
+  if (!play_dice(s, a.g, e, a.dice, d0, d1)) return 0;  // wave-uniform
+  Legal l;
+  legal2(s, d0, d1, l);
+  const int total = aft_entries(s, d0, d1, l, L, lane);
+  const int64_t row0 = kFill ? (int64_t)a.offsets[e] : 0;
+  ValRoot vr;
+  if constexpr (kScore) {
+    if (total == 0) return 0;  // wave-uniform: no play, nothing to score
+    val_root(vr, *vn, *VS, a.pl.p0[e], a.pl.p1[e], lane);
+  }
+  return aft_chunks(l, total, L, lane, [&](int nkept, bool keep, int rank, int nnew, const Play& y) {
     if constexpr (kFill) {
       const int64_t R = row0 + nkept + rank;
       if (keep) {
@@ -128,15 +163,20 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
           if (a.codes)
             reinterpret_cast<uint32_t*>(a.codes)[R] = (uint32_t)(uint16_t)c1 | ((uint32_t)(uint16_t)c2 << 16);
           aft_store_row(a.row_env, a.reward, a.obs, R, e, rew, c);
+          if constexpr (kRec) {
+            uint4 ra, rb;
+            side_to_record(c, ra, rb);
+            rb.w = (uint32_t)rew;
+            ar->rec[2 * R] = ra;
+            ar->rec[2 * R + 1] = rb;
+            if (rew != 0) ar->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+          }
         }
       }
       if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + nkept, nnew, *S, lane);
       if constexpr (kScore) val_score_rows(*vn, *VS, vr, a.cap, row0 + nkept, nnew, lane);
     }
-    nkept += nnew;
-    wave_lds_handoff();  // the keys, to the next chunk
-  }
-  return nkept;
+  });
 }
 
 __global__ void __launch_bounds__(kAftCountBlock) k_aft_count(AftArgs a) {

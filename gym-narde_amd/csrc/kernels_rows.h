@@ -200,14 +200,13 @@ __device__ __forceinline__ void val_stage_row(const ValNet& n, ValStage& S, cons
   }
 }
 
-// the values of the nnew rows a chunk staged -> value rows Rbase .. Rbase +
-// nnew - 1, below cap, kValRows rows at a time (a short batch repeats the
-// last row).  All lanes of the wave call it with the same arguments.
-__device__ __forceinline__ void val_score_rows(const ValNet& n, ValStage& S, const ValRoot& r, int64_t cap,
-                                               int64_t Rbase, int nnew, int lane) {
+// the values of the first nr rows a chunk staged, kValRows rows at a time (a
+// short batch repeats the last row): out(q, v) from lane 0 of the lane group
+// that scored staged row q, terminal rows left out.  All lanes of the wave
+// call it with the same arguments.
+template <typename F>
+__device__ __forceinline__ void val_rows_each(const ValNet& n, ValStage& S, const ValRoot& r, int nr, F&& out) {
   wave_lds_handoff();  // the lists, to every lane
-  const int64_t room = cap - Rbase;
-  const int nr = room < (int64_t)nnew ? (int)room : nnew;  // wave-uniform: the rest is past cap
   val_units(r.nu, [&](auto NU) {
     for (int q0 = 0; q0 < nr; q0 += kValRows) {
       const int q = min(q0 + r.g, nr - 1);
@@ -221,10 +220,19 @@ __device__ __forceinline__ void val_score_rows(const ValNet& n, ValStage& S, con
       float part = val_lane_part<NU.value>(z, r.w2, n.hidden_act);
 #pragma unroll
       for (int o = kValLanes / 2; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
-      if (r.t == 0 && q0 + r.g < nr && cnt >= 0) n.value[Rbase + q] = val_out_act(r.b2 + part, n.out_act);
+      if (r.t == 0 && q0 + r.g < nr && cnt >= 0) out(q, val_out_act(r.b2 + part, n.out_act));
     }
   });
   wave_lds_handoff();  // the next chunk's lists are staged behind these reads
+}
+
+// the values of the nnew rows a chunk staged -> value rows Rbase .. Rbase +
+// nnew - 1, below cap.  All lanes of the wave call it with the same arguments.
+__device__ __forceinline__ void val_score_rows(const ValNet& n, ValStage& S, const ValRoot& r, int64_t cap,
+                                               int64_t Rbase, int nnew, int lane) {
+  const int64_t room = cap - Rbase;
+  const int nr = room < (int64_t)nnew ? (int)room : nnew;  // wave-uniform: the rest is past cap
+  val_rows_each(n, S, r, nr, [&](int q, float v) { n.value[Rbase + q] = v; });
 }
 
 // ------------------------------------------------------------ counts -> offsets

@@ -22,6 +22,8 @@
 //                       MLP in the fill pass), k_aft_scan, k_aft_pick
 //   kernels_afterstates.h  REF2 afterstates: the play enumeration
 //                       (k_aft_count, k_aft_fill, k_aft_fill_scored)
+//   kernels_lookahead.h  REF2 two-ply lookahead: the record fill and the
+//                       expected-best-reply pass (k_aft_fill_rec, k_aft_look)
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
 //                       (k_turn_count, k_turn_fill, k_turn_overflow, and the
 //                       scored fills)
@@ -53,6 +55,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_agent.h"
 #include "kernels_rows.h"
 #include "kernels_afterstates.h"
+#include "kernels_lookahead.h"
 #include "kernels_turn_afterstates.h"
 #include "kernels_td.h"
 
@@ -720,6 +723,43 @@ int narde_afterstates_scored(narde_env* e, const uint8_t* dice, int64_t cap, int
   return expand_plays(e, AftArgs{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, nullptr, nullptr,
                                  reward},
                       &vn, (hipStream_t)stream);
+}
+
+int narde_afterstates_lookahead(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
+                                int16_t* codes, int8_t* reward, const narde_value_mlp* net, int perspective,
+                                float* value, void* scratch, int64_t scratch_bytes, void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, kAftMaxPlays, nullptr, nullptr, codes, 4,
+                                  "codes must be 4-B aligned"))
+    return rc;
+  ValNet vn;
+  if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
+  if (perspective != 1) return fail(NARDE_EINVAL, "perspective must be 1 (white's values)");
+  if (!scratch) return fail(NARDE_EINVAL, "NULL argument");
+  // (32 x cap overflows for no cap a caller can hold rows for: compare in rows)
+  if (scratch_bytes < 0 || scratch_bytes / 32 < cap)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below NARDE_LOOKAHEAD_SCRATCH_BYTES = 32 x cap %lld",
+                (long long)scratch_bytes, (long long)cap);
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  const AftArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, nullptr, nullptr, reward};
+  const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
+  k_aft_count<<<(unsigned)((e->n + cw - 1) / cw), kAftCountBlock, 0, st>>>(a);
+  if (const int rc = check_launch("k_aft_count")) return rc;
+  k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
+  if (const int rc = check_launch("k_aft_scan")) return rc;
+  if (cap == 0) return NARDE_OK;
+  k_aft_fill_rec<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a, AftRec{(uint4*)scratch, value});
+  if (const int rc = check_launch("k_aft_fill_rec")) return rc;
+  // over cap rows (the count is on the device), never more than the rows B envs can have
+  const int64_t bound = e->n * (int64_t)kAftMaxPlays;
+  const int64_t rows = cap < bound ? cap : bound;
+  const LookArgs la{(const uint4*)scratch, offsets, (int)e->n, cap, e->dice_mode};
+  if (rows <= kLookSplitRows)  // a short launch: a row's rolls over kLookSplit waves (the same bits)
+    k_aft_look<kLookSplit><<<(unsigned)rows, 64 * kLookSplit, 0, st>>>(la, vn);
+  else
+    k_aft_look<1><<<(unsigned)rows, 64, 0, st>>>(la, vn);
+  return check_launch("k_aft_look");
 }
 
 int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* codes, int64_t cap,

@@ -26,6 +26,13 @@ def td_scratch_floats(num_envs, hidden):
     """NARDE_TD_SCRATCH_FLOATS: narde_value_td_apply's scratch."""
     b = int(num_envs)
     return (b + 3) // 4 * 4 + (b + TD_SLAB - 1) // TD_SLAB * (200 * int(hidden) + 4)
+
+
+def lookahead_scratch_bytes(cap):
+    """NARDE_LOOKAHEAD_SCRATCH_BYTES: narde_afterstates_lookahead's scratch."""
+    return 32 * int(cap)
+
+
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
 
@@ -93,6 +100,8 @@ SIGNATURES = {
     "narde_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp]),
     "narde_turn_afterstates_scored": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
                                              _vp]),
+    "narde_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp,
+                                           _i64, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

@@ -10,7 +10,9 @@ On a rules="full4" env the rows are whole turns (turn_afterstates(),
 pick_turn()): four sub-moves on doubles, the max-dice-used rule.
 With a value_net.ValueMLP the rows are scored inside the expansion
 (scored_afterstates() / scored_turn_afterstates(): one float a row, the
-198-float rows never made).
+198-float rows never made).  plies=2 searches one ply deeper
+(lookahead_afterstates(): each row's value is the expectation, over the
+opponent's rolls, of the opponent's best reply under the same net).
 """
 
 
@@ -24,9 +26,10 @@ class ValuePlayer:
     False -- never (every step as with any other module); True -- required
     (a TypeError for another module).  cap: the rows every step's arrays
     hold (fused only); with it a step makes no synchronise, and rows past
-    cap are not played."""
+    cap are not played.  plies: 1 -- the rows' own values; 2 -- their
+    two-ply values (the fused path, perspective "white", rules="ref2")."""
 
-    def __init__(self, env, net, perspective="white", fused=None, cap=None):
+    def __init__(self, env, net, perspective="white", fused=None, cap=None, plies=1):
         from .vector import PERSPECTIVES
 
         if perspective not in PERSPECTIVES:
@@ -42,6 +45,18 @@ class ValuePlayer:
             raise ValueError("cap is the fused path's")
         self.cap = None if cap is None else int(cap)
         self._scored = env.scored_turn_afterstates if env.full else env.scored_afterstates
+        if plies not in (1, 2):
+            raise ValueError("plies must be 1 or 2")
+        if plies == 2:
+            if not is_mlp:
+                raise TypeError("plies=2 needs a gym_narde.value_net.ValueMLP")
+            if not self.fused:
+                raise ValueError("plies=2 is the fused path's")
+            if perspective != "white":
+                raise ValueError('plies=2 needs perspective "white"')
+            if env.full:
+                raise ValueError('plies=2 is rules="ref2" only')
+        self.plies = plies
 
     def values(self, aft):
         """net(feat), with the rows that end the game set to their known
@@ -69,7 +84,9 @@ class ValuePlayer:
         path aft.feat is None."""
         env = self.env
         dice = env.dice()
-        if self.fused:
+        if self.plies == 2:
+            aft, values = env.lookahead_afterstates(self.net, dice, cap=self.cap)
+        elif self.fused:
             aft, values = self._scored(self.net, dice, cap=self.cap, perspective=self.perspective)
         else:
             aft = self._expand(dice)

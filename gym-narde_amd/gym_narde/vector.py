@@ -158,6 +158,7 @@ class VecNardeEnv:
         self.legal = torch.zeros(B, dtype=torch.int64, **z)
         self.actions_used = torch.zeros((B, 2), dtype=torch.int16, **z)
         self.played = torch.zeros(B, dtype=torch.int64, **z)
+        self._look_scratch = None  # lookahead_afterstates()' row records, made on its first call
         # per-call plumbing of step(), resolved once: the bound entry point and
         # the output buffers' pointers (they never move)
         lib = self.handle.lib
@@ -383,9 +384,10 @@ class VecNardeEnv:
         self._keep = (d,)
         return out._replace(cap=cap)
 
-    def _scored_rows(self, k, net, dice, cap, perspective, out):
+    def _scored_rows(self, k, net, dice, cap, perspective, out, lookahead=False):
         """scored_afterstates() / scored_turn_afterstates(): the rows of kind
-        k with their values under net in place of feat and obs."""
+        k with their values under net in place of feat and obs.  lookahead:
+        the two-ply values (lookahead_afterstates())."""
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
         B, t = self.num_envs, self.torch
@@ -431,8 +433,17 @@ class VecNardeEnv:
             self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
         else:
             rows = (out.row_env, getattr(out, k.field), out.reward)
-            self.handle.call(k.expand + "_scored", _lib.ptr(d), cap, _lib.ptr(offsets), *(_lib.ptr(a) for a in rows),
-                             ctypes.byref(mlp), PERSPECTIVES[perspective], _lib.ptr(values), self._s())
+            if lookahead:
+                need = _lib.lookahead_scratch_bytes(cap)
+                if self._look_scratch is None or self._look_scratch.numel() < need:  # grown only when cap grows
+                    self._look_scratch = t.empty(need, dtype=t.uint8, device=self.device)
+                self.handle.call(k.expand + "_lookahead", _lib.ptr(d), cap, _lib.ptr(offsets),
+                                 *(_lib.ptr(a) for a in rows), ctypes.byref(mlp), PERSPECTIVES[perspective],
+                                 _lib.ptr(values), _lib.ptr(self._look_scratch), self._look_scratch.numel(), self._s())
+            else:
+                self.handle.call(k.expand + "_scored", _lib.ptr(d), cap, _lib.ptr(offsets),
+                                 *(_lib.ptr(a) for a in rows), ctypes.byref(mlp), PERSPECTIVES[perspective],
+                                 _lib.ptr(values), self._s())
         self._keep = (d, net)
         return out._replace(cap=cap), values[:cap]
 
@@ -454,6 +465,24 @@ class VecNardeEnv:
         if self.full:
             raise ValueError('scored_afterstates() is rules="ref2" only')
         return self._scored_rows(_REF2_ROWS, net, dice, cap, perspective, out)
+
+    def lookahead_afterstates(self, net, dice=None, cap=None, out=None):
+        """scored_afterstates() one ply deeper (narde_afterstates_lookahead;
+        DESIGN.md section 17): the same rows, and for values white's two-ply
+        value of each -- the mean, over the opponent's rolls in the env's dice
+        mode, of the opponent's best reply under net (the smallest of the
+        replies' one-ply values when black replies, the largest when white
+        does; a roll with no reply takes the position step((0, 0)) leaves:
+        the row's position with the mover flipped, include/narde.h has the one
+        exception); a terminal row's is its outcome.  Returns (aft, values)
+        shaped as scored_afterstates() returns them, the perspective "white";
+        cap / out as there: cap None makes the one synchronise, cap or out
+        given none (graph-safe).  The rows' records between the call's two
+        passes live in a scratch tensor kept on the env, grown only when cap
+        grows (so: outside capture, once, for the largest cap)."""
+        if self.full:
+            raise ValueError('lookahead_afterstates() is rules="ref2" only')
+        return self._scored_rows(_REF2_ROWS, net, dice, cap, "white", out, lookahead=True)
 
     def scored_turn_afterstates(self, net, dice=None, cap=None, perspective="white", out=None):
         """rules="full4": scored_afterstates() over turn_afterstates()' rows

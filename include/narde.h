@@ -413,7 +413,52 @@ int narde_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t cap, i
                              int32_t *row_env, int16_t *codes, int8_t *reward,
                              const narde_value_mlp *net, int perspective, float *value, void *stream);
 
-/* The same over narde_turn_afterstates' rows (FULL4), the overflow path
+/* Two-ply lookahead over narde_afterstates_scored's rows (REF2; DESIGN.md
+ * section 17).  The rows, their order, offsets, row_env, codes, reward, the
+ * cap rule and dice == NULL are exactly that call's.  value[r] is WHITE's
+ * value of row r:
+ *   a terminal row (reward != 0): its outcome, as the scored call gives it;
+ *   any other row: the mean, over the opponent's ordered rolls (a, b) in the
+ *   env's dice mode (36 pairs for NARDE_DICE_ALL36, the 30 unequal ones for
+ *   NARDE_DICE_NODOUBLES, equal weight each), of the best reply m(r, a, b).
+ * Let s_r be the position row r leaves: its record after the step, the
+ * mover flipped, the first-turn flags as narde_step leaves them.  If s_r
+ * with the roll (a, b) has rows in narde_afterstates' sense, m is the
+ * smallest of their narde_afterstates_scored values (perspective 1) when
+ * the side to reply is black, the largest when it is white; terminal
+ * replies enter with their outcome.  If it has none, m is the value (a
+ * terminal one: the outcome) of the position narde_step(actions = (0, 0),
+ * that roll, autoreset = 0) leaves.  That is s_r with the mover flipped --
+ * a pass -- with one exception, which the step's own result defines: code 0
+ * is the bear-off from point 0, so where that move is legal and every play
+ * that starts with it needs a second move no code can express, the step
+ * bears the checker off (and a second one from point 0 if the other die
+ * allows) although no row says so (4 of the 7,732 no-reply (row, roll)
+ * pairs of tests/test_lookahead_cpu.py).  The TimeLimit is not looked at.
+ * The rolls are evaluated as the 36 (30) ordered pairs: (a, b) and (b, a)
+ * can leave different afterstates (narde_env.py:63-83 drops the first die
+ * in roll order when a bear-off's distance is not rolled).
+ * perspective must be 1: the mover's values have no successor sign under a
+ * bounded output (narde_value_td_apply's reason).
+ * The same inputs give the same bits on every call, whatever cap: no float
+ * atomics, a row's per-roll values are summed by one lane in the order a
+ * outer, b inner, in double, the mean rounded to float once.
+ * scratch: device memory, 16-B aligned, scratch_bytes >=
+ * NARDE_LOOKAHEAD_SCRATCH_BYTES(cap): the rows' 32-byte records, kept
+ * between the call's passes; its contents afterwards are unspecified.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable: the
+ * lookahead pass is launched over cap rows (never more than the rows B envs
+ * can have) and its waves leave at or past min(offsets[B], cap); nothing at
+ * or past cap is touched.  NARDE_EINVAL before any device call:
+ * narde_afterstates_scored's cases, perspective != 1, a NULL, too small or
+ * misaligned scratch. */
+#define NARDE_LOOKAHEAD_SCRATCH_BYTES(cap) (32 * (int64_t)(cap))
+int narde_afterstates_lookahead(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                                int32_t *row_env, int16_t *codes, int8_t *reward,
+                                const narde_value_mlp *net, int perspective, float *value,
+                                void *scratch, int64_t scratch_bytes, void *stream);
+
+/* narde_afterstates_scored over narde_turn_afterstates' rows (FULL4), the overflow path
  * included; that call's workspace rule holds (the handle's first call of
  * either, outside capture). */
 int narde_turn_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
