@@ -9,10 +9,12 @@ device: VecNardeEnv.afterstates -> net -> pick_afterstate -> step
 turn_afterstates -> net -> pick_turn -> step).  --fused: the net becomes a
 value_net.ValueMLP and the rows are scored inside the expansion
 (scored_afterstates / scored_turn_afterstates: one float a row, the 198-float
-rows never made).  --depth 2 (ref2, implies --fused): a two-ply search --
-every afterstate is valued by the expectation, over the opponent's rolls, of
-the opponent's best reply under the same net (lookahead_afterstates; --plies
-is already the number of plies played).
+rows never made).  --depth 2 (either rule set, implies --fused): a two-ply
+search -- every afterstate is valued by the expectation, over the opponent's
+rolls, of the opponent's best reply under the same net (value_play's
+LookaheadPlayer: lookahead_afterstates, --rules full4:
+lookahead_turn_afterstates over whole-turn replies; --plies is already the
+number of plies played).
 
   python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2]
 """
@@ -37,7 +39,7 @@ def make_net(seed, device):
 def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False, depth=1):
     import torch
 
-    from gym_narde.value_play import ValuePlayer
+    from gym_narde.value_play import LookaheadPlayer, ValuePlayer
     from gym_narde.vector import VecNardeEnv
 
     env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
@@ -53,7 +55,7 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         from gym_narde.value_net import ValueMLP
 
         net = ValueMLP.from_sequential(net)
-    player = ValuePlayer(env, net, perspective="white", plies=depth)
+    player = LookaheadPlayer(env, net) if depth == 2 else ValuePlayer(env, net, perspective="white")
     eps = torch.tensor(epsilon, dtype=torch.float32, device=env.device) if epsilon > 0 else None
     rows = 0
     for ply in range(plies):
@@ -76,6 +78,7 @@ if __name__ == "__main__":
     ap.add_argument("--weights", default=None)
     ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
     ap.add_argument("--fused", action="store_true")
-    ap.add_argument("--depth", type=int, choices=(1, 2), default=1)
+    ap.add_argument("--depth", type=int, choices=(1, 2), default=1,
+                    help="2: value every afterstate by the opponent's expected best reply (ref2 and full4)")
     a = ap.parse_args()
     main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused, depth=a.depth)

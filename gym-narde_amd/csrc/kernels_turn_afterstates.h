@@ -74,21 +74,78 @@ struct alignas(16) TurnFrontLds {  // per wave, fast path
   uint32_t path[2][kTurnFront];
 };
 
-// env e's rows (all lanes of the wave call it with the same e); returns the
-// number of rows, or -1 if a level outgrew `room` nodes (nothing written).
+// What the record fill (kernels_turn_lookahead.h) writes besides the narrow
+// outputs: row R's 128-B piece of the lookahead's scratch -- the record after
+// the turn, its ply-counter word replaced by the reward (the later passes
+// read it as "terminal"), and the word of rolls to redo cleared -- and a
+// terminal row's outcome in white's perspective.
+constexpr int kTurnLookRowWords = 32;   // 128 B a row
+constexpr int kTurnLookBest = 8;        // word 8 .. 28: the 21 unordered rolls' bests
+constexpr int kTurnLookRedo = 29;       // word 29: bit k = roll k outgrew the fast frontier
+struct TurnRec {
+  uint32_t* __restrict__ row;  // [cap][kTurnLookRowWords]
+  float* __restrict__ value;   // [cap]
+};
+
+// The reducing consumer (kernels_turn_lookahead.h): the position and the roll
+// the walk starts from in place of an env's, the root forward of that
+// position, the replier's side, and the best of the final level's values,
+// which the walk leaves here.
+struct TurnLook {
+  Side s;
+  int d0, d1;
+  const ValRoot* vr;
+  bool smallest;
+  float best;
+};
+__device__ __forceinline__ float turn_look_level(const Side& s, const TurnRoot& r, const uint32_t* pcur, int nrows,
+                                                 int level, const ValNet& vn, ValStage& VS, const TurnLook& lk, int lane);
+
+// the position a walk starts from: env e's record, or the reducing consumer's
+template <bool kLook>
+__device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const TurnLook* lk) {
+  if constexpr (kLook) {
+    return lk->s;
+  } else {
+    return side_from_record(a.pl.p0[e], a.pl.p1[e]);
+  }
+}
+
+// The level walk of a position under a roll (all lanes of the wave call it
+// with the same arguments), and what is done with its final level -- the
+// consumers, chosen at compile time.  Returns the number of rows (0: a pass,
+// or a die outside 1..6), or -1 if a level outgrew `room` nodes (nothing
+// written, nothing reduced).
 // key: room + 2 keys of the level being built; pathA, pathB: the two level
 // buffers, room paths each.
+// The position is env e's record and the roll its dice, or, kLook, lk's (a
+// and e are then not looked at).
 // kFill: write the rows from row a.offsets[e] on, below a.cap.
 // kScore (a fill with a.feat NULL): the rows' values under vn as well
-// (kernels_rows.h "the scored rows"; VS the wave's lists).
-template <bool kFill, bool kScore = false>
+// (kernels_rows.h "the scored rows"; VS the wave's lists).  kRec (a fill
+// with a.feat NULL): the rows' records to *tr as well.  kLook (no fill): the
+// rows' values under vn against lk->vr reduced to the replier's best, left in
+// lk->best.
+// (The walk and its consumers are one function on purpose, and the existing
+// instantiations compile to the instructions they had: with the walk a
+// function of its own that hands the final level to its callers -- by
+// reference, as a struct, through a callback, or with env e's load in a
+// wrapper -- k_turn_overflow_scored ran 2 to 7 % and k_turn_fill_scored up to
+// 2 % slower than before, outside the runs' spread; DESIGN.md section 18.2,
+// MEASUREMENT_LOG M.34.)
+template <bool kFill, bool kScore = false, bool kRec = false, bool kLook = false>
 __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt, uint32_t* pathA, uint32_t* pathB,
                                         int room, TurnScan& L, AftStage* S, const ValNet* vn = nullptr,
-                                        ValStage* VS = nullptr) {
+                                        ValStage* VS = nullptr, const TurnRec* tr = nullptr, TurnLook* lk = nullptr) {
   const int lane = threadIdx.x & 63;
-  const Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
+  const Side s = turn_position<kLook>(a, e, lk);
   int d0, d1;
-  if (!play_dice(s, a.g, e, a.dice, d0, d1)) return 0;  // wave-uniform
+  if constexpr (kLook) {
+    d0 = lk->d0;
+    d1 = lk->d1;
+  } else {
+    if (!play_dice(s, a.g, e, a.dice, d0, d1)) return 0;  // wave-uniform
+  }
   const TurnRoot r = turn_root(s, d0, d1);
   const bool two = r.dh != r.dl;
   uint32_t* pcur = pathA;
@@ -204,11 +261,22 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         if (a.reward) a.reward[R] = (int8_t)rew;
         if (a.row_env) a.row_env[R] = e;
         if (a.obs) store_obs(a.obs, (size_t)R, c);
+        if constexpr (kRec) {
+          uint4 ra, rb;
+          side_to_record(c, ra, rb);
+          rb.w = (uint32_t)rew;
+          uint4* const row = reinterpret_cast<uint4*>(tr->row + R * kTurnLookRowWords);
+          row[0] = ra;
+          row[1] = rb;
+          tr->row[R * kTurnLookRowWords + kTurnLookRedo] = 0u;
+          if (rew != 0) tr->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+        }
       }
       if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + g0, min(64, nrows - g0), *S, lane);
       if constexpr (kScore) val_score_rows(*vn, *VS, vr, a.cap, row0 + g0, min(64, nrows - g0), lane);
     }
   }
+  if constexpr (kLook) lk->best = turn_look_level(s, r, pcur, nrows, level, *vn, *VS, *lk, lane);
   return nrows;
 }
 

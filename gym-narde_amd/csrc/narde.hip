@@ -27,6 +27,10 @@
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
 //                       (k_turn_count, k_turn_fill, k_turn_overflow, and the
 //                       scored fills)
+//   kernels_turn_lookahead.h  FULL4 two-ply lookahead: the record fills, the
+//                       reply walk per (row, roll), its overflow pass and the
+//                       mean (k_turn_fill_rec, k_turn_look, k_turn_look_overflow,
+//                       k_turn_look_mean)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
 // This file keeps the handle, the host-side checks and every C entry point.
@@ -57,6 +61,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_afterstates.h"
 #include "kernels_lookahead.h"
 #include "kernels_turn_afterstates.h"
+#include "kernels_turn_lookahead.h"
 #include "kernels_td.h"
 
 namespace {
@@ -247,9 +252,11 @@ int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t s
 }
 
 // FULL4's: the handle's workspace on its first call, the count passes, the
-// scan, the fills (scored with vn)
+// scan, the fills (scored with vn; with tr the record fills of the lookahead,
+// whose own passes the caller launches behind them)
 int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env, int8_t* play,
-                 float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st) {
+                 float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st,
+                 const TurnRec* tr = nullptr) {
   if (!e->turn_slab) {
     // the workspace belongs to the handle and is made once, outside capture
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -276,7 +283,13 @@ int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offset
   if (const int rc = check_launch("k_turn_overflow<count>")) return rc;
   k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
   if (const int rc = check_launch("k_aft_scan")) return rc;
-  if (cap == 0 || !(row_env || play || feat || obs || reward || vn)) return NARDE_OK;
+  if (cap == 0 || !(row_env || play || feat || obs || reward || vn || tr)) return NARDE_OK;
+  if (tr) {
+    k_turn_fill_rec<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a, *tr);
+    if (const int rc = check_launch("k_turn_fill_rec")) return rc;
+    k_turn_overflow_rec<<<kTurnOvfWaves, 64, 0, st>>>(a, *tr);
+    return check_launch("k_turn_overflow_rec");
+  }
   if (vn) {
     k_turn_fill_scored<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a, *vn);
     if (const int rc = check_launch("k_turn_fill_scored")) return rc;
@@ -789,6 +802,44 @@ int narde_turn_afterstates_scored(narde_env* e, const uint8_t* dice, int64_t cap
   if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
   DeviceGuard dg(e->device);
   return expand_turns(e, dice, cap, offsets, row_env, play, nullptr, nullptr, reward, &vn, (hipStream_t)stream);
+}
+
+int narde_turn_afterstates_lookahead(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets,
+                                     int32_t* row_env, int8_t* play, int8_t* reward, const narde_value_mlp* net,
+                                     int perspective, float* value, void* scratch, int64_t scratch_bytes,
+                                     void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, NARDE_TURN_AFT_MAX, nullptr, nullptr, play, 8,
+                                  "play must be 8-B aligned"))
+    return rc;
+  ValNet vn;
+  if (const int rc = check_value_net(net, perspective, value, vn)) return rc;
+  if (perspective != 1) return fail(NARDE_EINVAL, "perspective must be 1 (white's values)");
+  if (!scratch) return fail(NARDE_EINVAL, "NULL argument");
+  // (128 x cap overflows for no cap a caller can hold rows for: compare in rows)
+  if (scratch_bytes < 0 || scratch_bytes / (4 * kTurnLookRowWords) < cap)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES = 128 x cap %lld",
+                (long long)scratch_bytes, (long long)cap);
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  const TurnRec tr{(uint32_t*)scratch, value};
+  if (const int rc = expand_turns(e, dice, cap, offsets, row_env, play, nullptr, nullptr, reward, nullptr, st, &tr))
+    return rc;
+  if (cap == 0) return NARDE_OK;
+  // over cap rows (the count is on the device), never more than the rows B envs can have
+  const int64_t bound = e->n * (int64_t)NARDE_TURN_AFT_MAX;
+  const int64_t rows = cap < bound ? cap : bound;
+  const TurnLookArgs la{(uint32_t*)scratch, offsets, (int)e->n, cap, e->dice_mode, e->turn_slab};
+  if (rows <= kTurnLookSplitRows)  // a short launch: a row's rolls over kTurnLookSplit waves (the same bits)
+    k_turn_look<kTurnLookSplit><<<(unsigned)rows, 64 * kTurnLookSplit, 0, st>>>(la, vn);
+  else
+    k_turn_look<1><<<(unsigned)rows, 64, 0, st>>>(la, vn);
+  if (const int rc = check_launch("k_turn_look")) return rc;
+  k_turn_look_overflow<<<kTurnOvfWaves, 64, 0, st>>>(la, vn);
+  if (const int rc = check_launch("k_turn_look_overflow")) return rc;
+  k_turn_look_mean<<<(unsigned)((rows + kTurnLookMeanBlock - 1) / kTurnLookMeanBlock), kTurnLookMeanBlock, 0, st>>>(
+      la, value);
+  return check_launch("k_turn_look_mean");
 }
 
 int narde_value_td_trace(narde_env* e, const narde_value_mlp_train* net, float decay, float* trace, int64_t ld_trace,

@@ -33,6 +33,11 @@ def lookahead_scratch_bytes(cap):
     return 32 * int(cap)
 
 
+def turn_lookahead_scratch_bytes(cap):
+    """NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES: narde_turn_afterstates_lookahead's scratch."""
+    return 128 * int(cap)
+
+
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
 
@@ -102,6 +107,8 @@ SIGNATURES = {
                                              _vp]),
     "narde_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp,
                                            _i64, _vp]),
+    "narde_turn_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
+                                                _vp, _i64, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

@@ -12,7 +12,9 @@ With a value_net.ValueMLP the rows are scored inside the expansion
 (scored_afterstates() / scored_turn_afterstates(): one float a row, the
 198-float rows never made).  plies=2 searches one ply deeper
 (lookahead_afterstates(): each row's value is the expectation, over the
-opponent's rolls, of the opponent's best reply under the same net).
+opponent's rolls, of the opponent's best reply under the same net);
+LookaheadPlayer is that search for either rule set
+(lookahead_turn_afterstates() on a rules="full4" env).
 """
 
 
@@ -57,6 +59,7 @@ class ValuePlayer:
             if env.full:
                 raise ValueError('plies=2 is rules="ref2" only')
         self.plies = plies
+        self._lookahead = env.lookahead_afterstates
 
     def values(self, aft):
         """net(feat), with the rows that end the game set to their known
@@ -85,7 +88,7 @@ class ValuePlayer:
         env = self.env
         dice = env.dice()
         if self.plies == 2:
-            aft, values = env.lookahead_afterstates(self.net, dice, cap=self.cap)
+            aft, values = self._lookahead(self.net, dice, cap=self.cap)
         elif self.fused:
             aft, values = self._scored(self.net, dice, cap=self.cap, perspective=self.perspective)
         else:
@@ -95,3 +98,18 @@ class ValuePlayer:
         obs, reward, terminated, truncated, info = env.step(actions)
         info = dict(info, dice=dice, row=row)
         return obs, reward, terminated, truncated, info, aft, values, actions
+
+
+class LookaheadPlayer(ValuePlayer):
+    """The two-ply player for either rule set: every row valued by the mean,
+    over the opponent's rolls, of the opponent's best reply under net (a
+    value_net.ValueMLP) -- lookahead_afterstates() on a rules="ref2" env,
+    lookahead_turn_afterstates() on a rules="full4" one.  The fused path,
+    perspective "white"; cap and step() as ValuePlayer's."""
+
+    def __init__(self, env, net, cap=None):
+        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+            raise TypeError("LookaheadPlayer needs a gym_narde.value_net.ValueMLP")
+        super().__init__(env, net, perspective="white", fused=True, cap=cap, plies=1)
+        self.plies = 2
+        self._lookahead = env.lookahead_turn_afterstates if env.full else env.lookahead_afterstates

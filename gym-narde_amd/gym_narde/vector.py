@@ -122,10 +122,13 @@ Afterstates = collections.namedtuple("Afterstates", "offsets row_env codes feat 
 # play (R,4,2) int8 (from, die) in place of the action codes
 TurnAfterstates = collections.namedtuple("TurnAfterstates", "offsets row_env play feat obs reward cap")
 # what differs between the two: the C entry points, the tuple, the action
-# column (field, trailing shape, torch dtype), the pick's fill for no row
-_RowKind = collections.namedtuple("_RowKind", "expand pick tuple field shape dtype no_row")
-_REF2_ROWS = _RowKind("narde_afterstates", "narde_afterstate_pick", Afterstates, "codes", (2,), "int16", 0)
-_FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAfterstates, "play", (4, 2), "int8", -1)
+# column (field, trailing shape, torch dtype), the pick's fill for no row,
+# the lookahead's scratch size
+_RowKind = collections.namedtuple("_RowKind", "expand pick tuple field shape dtype no_row look_scratch")
+_REF2_ROWS = _RowKind("narde_afterstates", "narde_afterstate_pick", Afterstates, "codes", (2,), "int16", 0,
+                      _lib.lookahead_scratch_bytes)
+_FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAfterstates, "play", (4, 2), "int8", -1,
+                       _lib.turn_lookahead_scratch_bytes)
 
 
 class VecNardeEnv:
@@ -158,7 +161,7 @@ class VecNardeEnv:
         self.legal = torch.zeros(B, dtype=torch.int64, **z)
         self.actions_used = torch.zeros((B, 2), dtype=torch.int16, **z)
         self.played = torch.zeros(B, dtype=torch.int64, **z)
-        self._look_scratch = None  # lookahead_afterstates()' row records, made on its first call
+        self._look_scratch = None  # the lookahead calls' row records, made on the first call
         # per-call plumbing of step(), resolved once: the bound entry point and
         # the output buffers' pointers (they never move)
         lib = self.handle.lib
@@ -387,7 +390,7 @@ class VecNardeEnv:
     def _scored_rows(self, k, net, dice, cap, perspective, out, lookahead=False):
         """scored_afterstates() / scored_turn_afterstates(): the rows of kind
         k with their values under net in place of feat and obs.  lookahead:
-        the two-ply values (lookahead_afterstates())."""
+        the two-ply values (lookahead_afterstates() / lookahead_turn_afterstates())."""
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
         B, t = self.num_envs, self.torch
@@ -434,7 +437,7 @@ class VecNardeEnv:
         else:
             rows = (out.row_env, getattr(out, k.field), out.reward)
             if lookahead:
-                need = _lib.lookahead_scratch_bytes(cap)
+                need = k.look_scratch(cap)
                 if self._look_scratch is None or self._look_scratch.numel() < need:  # grown only when cap grows
                     self._look_scratch = t.empty(need, dtype=t.uint8, device=self.device)
                 self.handle.call(k.expand + "_lookahead", _lib.ptr(d), cap, _lib.ptr(offsets),
@@ -490,6 +493,23 @@ class VecNardeEnv:
         if not self.full:
             raise ValueError('scored_turn_afterstates() is rules="full4" only')
         return self._scored_rows(_FULL4_ROWS, net, dice, cap, perspective, out)
+
+    def lookahead_turn_afterstates(self, net, dice=None, cap=None, out=None):
+        """rules="full4": scored_turn_afterstates() one ply deeper
+        (narde_turn_afterstates_lookahead): the same
+        rows, and for values white's two-ply value of each -- the mean, over
+        the opponent's rolls in the env's dice mode (the unordered rolls, a
+        double once and any other twice), of the opponent's best whole-turn
+        reply under net (the smallest of the replies' one-ply values when
+        black replies, the largest when white does; a roll with no legal
+        sub-move takes the row's position with the mover flipped); a terminal
+        row's is its outcome.  Every reply set is exact, the overflow paths
+        included.  Returns (aft, values) shaped as scored_turn_afterstates()
+        returns them, the perspective "white"; cap / out and the scratch
+        tensor as lookahead_afterstates()."""
+        if not self.full:
+            raise ValueError('lookahead_turn_afterstates() is rules="full4" only')
+        return self._scored_rows(_FULL4_ROWS, net, dice, cap, "white", out, lookahead=True)
 
     def _pick_rows(self, k, aft, values, perspective, epsilon, tag, seed):
         """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""

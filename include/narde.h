@@ -466,8 +466,54 @@ int narde_turn_afterstates_scored(narde_env *env, const uint8_t *dice, int64_t c
                                   const narde_value_mlp *net, int perspective, float *value,
                                   void *stream);
 
+/* Two-ply lookahead over narde_turn_afterstates_scored's rows (FULL4;
+ * DESIGN.md section 18).  The rows, their order, offsets, row_env, play,
+ * reward, the cap rule, dice == NULL and the workspace rule are exactly that
+ * call's.  value[r] is WHITE's value of row r:
+ *   a terminal row (reward != 0): its outcome, as the scored call gives it;
+ *   any other row: sum w m(r, roll) / sum w over the opponent's rolls.
+ * Let s_r be the position row r's play leaves under narde_step_full(play,
+ * dice, autoreset = 0): the mover flipped and both first-turn flags as that
+ * step leaves them (the side that moved has its flag cleared; the replier's
+ * decides the reply's head limit on 3-3, 4-4 and 6-6).  For a roll, the reply
+ * set is s_r's rows in narde_turn_afterstates' sense -- whole turns, the
+ * max-dice-used rule, two different dice with only one playable taking the
+ * higher die's nodes if it has any --, exact for every position (levels of up
+ * to NARDE_TURN_AFT_MAX nodes).  m is the smallest of the replies'
+ * narde_turn_afterstates_scored values (perspective 1) when the side to reply
+ * is black, the largest when it is white; terminal replies enter with their
+ * outcome.  A roll with no legal sub-move (a pass) takes the value of the
+ * position narde_step_full with an all -1 play leaves: always s_r with the
+ * mover flipped and nothing else changed -- FULL4 has no analogue of REF2's
+ * code-0 exception (all 784 pass (row, roll) pairs of
+ * tests/test_turn_lookahead_cpu.py).  The TimeLimit is not looked at.
+ * The dice of a roll are ordered before the turn is enumerated, so (a, b)
+ * and (b, a) give the same rows in the same order (checked against the
+ * oracle on that test's whole input set): the unordered rolls a <= b are
+ * evaluated, a outer ascending, b inner ascending, w = 1 for a double and 2
+ * otherwise (36 in all); under NARDE_DICE_NODOUBLES the 15 unequal rolls,
+ * equal weight each.
+ * perspective must be 1 (narde_afterstates_lookahead's reason).
+ * The same inputs give the same bits on every call, whatever cap and however
+ * the work is split over waves: no float atomics, every (row, roll) best is
+ * written by one wave to a slot of its own, and one thread sums a row's
+ * slots in that roll order in double and rounds the mean to float once.
+ * scratch: device memory, 16-B aligned, scratch_bytes >=
+ * NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES(cap): 128 B a row (its 32-byte record,
+ * the rolls' bests, the rolls to redo with a larger frontier); its contents
+ * afterwards are unspecified.  Stream-ordered, allocates nothing, no
+ * synchronise, graph-capturable once the handle's workspace exists; nothing at
+ * or past cap is touched.  NARDE_EINVAL before any device call:
+ * narde_turn_afterstates_scored's cases, perspective != 1, a NULL, too small
+ * or misaligned scratch. */
+#define NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES(cap) (128 * (int64_t)(cap))
+int narde_turn_afterstates_lookahead(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                                     int32_t *row_env, int8_t *play, int8_t *reward,
+                                     const narde_value_mlp *net, int perspective, float *value,
+                                     void *scratch, int64_t scratch_bytes, void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
- * section 16).  narde_value_mlp_train: narde_value_mlp's fields, the weights
+ * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
  * [hidden][ld_w1] (ld_w1 >= 198), w1[h * ld_w1 + c] = w1t[c * ld_w1t + h] --
  * a torch Linear(198, hidden).weight; NULL: none.  Every update writes w1t
