@@ -1,6 +1,7 @@
 """Random positions for differential tests (test_gpu_fuzz.py,
-test_full4_cpu.py): run-heavy boards where the block rule decides and
-bear-off endgames, placed for a random mover.  Test helper, not a test."""
+test_full4_cpu.py, test_gpu_afterstate_fuzz.py): run-heavy boards where the
+block rule decides and bear-off endgames, placed for a random mover.  Test
+helper, not a test."""
 import numpy as np
 from test_oracle_golden import _prime_boards
 
@@ -45,3 +46,46 @@ def random_positions(n, seed):
     off[blk] = off[blk][:, ::-1]
     ft = rng.integers(0, 2, (n, 2)).astype(np.uint8)
     return board, np.ascontiguousarray(off), ft, player, rng
+
+
+def _rolls(rng, n, doubles):
+    d0 = rng.integers(1, 7, n)
+    d1 = np.where(rng.random(n) < doubles, d0, rng.integers(1, 7, n))
+    return np.stack([d0, d1], 1).astype(np.uint8)
+
+
+def turn_states(n, seed, doubles=0.5):
+    """random_positions(n, seed) with a roll each, dice 1..6, a double with
+    probability `doubles` (a run-heavy board on a double is what outgrows the
+    turn kernels' 256-node frontier): the dict board, off, ft, player, dice
+    of tests/turn_afterstates_ref.py."""
+    board, off, ft, player, rng = random_positions(n, seed)
+    dice = _rolls(rng, n, doubles)
+    # endgame_boards leaves the opponent's 15 on the board, so a win there is
+    # always worth 2: on half of the endgame states the opponent has borne
+    # 1..14 off as well (taken from its points in ascending order), which
+    # makes the win worth 1
+    for i in range(n // 2, n):
+        if rng.random() < 0.5:
+            take = int(rng.integers(1, 15))
+            opp = -int(player[i])
+            for p in np.nonzero(board[i] * opp > 0)[0]:
+                c = min(take, abs(int(board[i, p])))
+                board[i, p] -= opp * c
+                take -= c
+                off[i, 0 if opp == 1 else 1] += c
+    return dict(board=board, off=off, ft=ft, player=player, dice=dice)
+
+
+def spread_replier_states(n, seed):
+    """turn_states(n, seed) with the run-heavy half's mover flipped and that
+    half's dice never a double: the piled side moves -- few first-ply rows --
+    and the spread side replies, whose doubles outgrow the lookahead's fast
+    frontier (with the piled side replying no reply walk does)."""
+    s = turn_states(n, seed)
+    h = n // 2
+    s["player"][:h] = -s["player"][:h]
+    d = s["dice"][:h]
+    same = d[:, 0] == d[:, 1]
+    d[same, 1] = d[same, 0] % 6 + 1
+    return s

@@ -75,6 +75,32 @@ def test_selfplay_states(selfplay):
     assert set(np.unique(ref["max_dice"])) >= {0, 1, 2, 3, 4}
 
 
+@pytest.fixture(scope="module")
+def fuzz(hc):
+    from fuzz_positions import turn_states
+
+    s = turn_states(1000, 505)
+    return s, check(hc, s)
+
+
+def test_positions_off_selfplay(fuzz):
+    """Run-heavy boards, half of them on a double, and bear-off endgames
+    (tests/fuzz_positions.py): what random play does not reach."""
+    s, (ref, got) = fuzz
+    cnt = np.diff(ref["offsets"])
+    rew = ref["reward"]
+    print(f"states {len(cnt)}, rows {int(cnt.sum())}, above 256 rows {int((cnt > 256).sum())}, most rows {int(cnt.max())}, "
+          f"most plays {int(ref['plays'].max())}, no row {int((cnt == 0).sum())}, reward 1 / 2 rows "
+          f"{int((rew == 1).sum())} / {int((rew == 2).sum())}")
+    assert (cnt > 256).sum() >= 100
+    # each of those has a level above the device's fast frontier (256 nodes): the overflow list's
+    assert (got["front"][cnt > 256] > 256).all()
+    assert set(np.unique(ref["max_dice"])) >= {0, 1, 2, 3, 4}
+    assert (rew == 1).any() and (rew == 2).any()
+    assert (cnt == 0).any()
+    assert (ref["plays"] > cnt).any()
+
+
 def test_golden_full4_states(hc):
     g = golden("full4.npz")
     check(hc, R.golden_states(g))

@@ -34,6 +34,7 @@ P = lambda a: a.ctypes.data_as(ctypes.c_void_p)  # noqa: E731
 # (hidden, g_hid, g_out, seed): the issue's sizes
 NETS = [(80, "sigmoid", "sigmoid", 1), (1, "relu", "none", 3), (65, "relu", "tanh", 4), (128, "tanh", "none", 2)]
 GOLDEN_STRIDE = 150  # of tests/golden/full4.npz: 111 states
+SPREAD_SEED = 711  # spread_replier_states(16, .): 142 rows, 64 (row, roll) pairs above 256 reply rows on 15 rows
 
 
 @pytest.fixture(scope="module")
@@ -152,9 +153,10 @@ def test_roll_order_does_not_matter(case):
             assert np.array_equal(x[key], y[key]), (TL.ROLLS[k], key)
 
 
-@pytest.mark.parametrize("spec", NETS, ids=lambda s: f"{s[0]}-{s[1]}-{s[2]}")
-def test_lookahead_through_the_shared_functions(hc, case, spec):
-    st, c = case
+def compare_with_reference(hc, st, c, spec):
+    """The host build on st against the reference case c, net spec: rows,
+    records, reply counts, terminal marks, values within 8 E.  Returns (got,
+    want, tol)."""
     ref, live = c["ref"], c["live"]
     net = make_net(*spec)
     got = host_lookahead(hc, st, net)
@@ -170,7 +172,7 @@ def test_lookahead_through_the_shared_functions(hc, case, spec):
     ends = np.zeros(cnt.shape, np.uint8)  # a reply of the (row, roll) ends the game
     for q, r in enumerate(c["replies"]):
         ends[np.repeat(np.arange(cnt.shape[0]), cnt[:, q])[r["reward"] != 0], q] = 1
-    assert np.array_equal(got["terminal"][live][:, c["ks"]], ends) and ends.any()
+    assert np.array_equal(got["terminal"][live][:, c["ks"]], ends)
     want, w32, m64 = TL.two_ply_weighted(net, c["replies"], c["ks"], c["rec"][3] == -1)
     E = TL.error_bound(w32, want)
     tol = TOL_FACTOR * E
@@ -186,6 +188,32 @@ def test_lookahead_through_the_shared_functions(hc, case, spec):
     # and the values are not the one-ply ones
     one = TL.LR.copy.deepcopy(net).double()(torch.from_numpy(ref["feat"][live]).double()).detach().numpy().reshape(-1)
     assert np.abs(one - want).max() > 1e3 * tol
+    return got, ends
+
+
+@pytest.mark.parametrize("spec", NETS, ids=lambda s: f"{s[0]}-{s[1]}-{s[2]}")
+def test_lookahead_through_the_shared_functions(hc, case, spec):
+    st, c = case
+    got, ends = compare_with_reference(hc, st, c, spec)
+    assert ends.any()
+
+
+def test_spread_repliers_off_selfplay(hc):
+    """Run-heavy boards with the piled side to move and the spread side
+    replying (tests/fuzz_positions.py): reply walks that outgrow the fast
+    frontier by the dozen, several rolls of one row among them."""
+    from fuzz_positions import spread_replier_states
+
+    st = spread_replier_states(16, SPREAD_SEED)
+    c = TL.reference_case(st)
+    cnt = reply_counts(c)
+    big = cnt > 256
+    print(f"rows {len(c['live'])}, reply rows {int(cnt.sum())}, (row, roll) pairs above 256 reply rows {int(big.sum())}, "
+          f"rows with two or more {int((big.sum(1) >= 2).sum())}")
+    assert big.sum() >= 30 and (big.sum(1) >= 2).any()
+    got, _ = compare_with_reference(hc, st, c, NETS[0])
+    # a (row, roll) with more than 256 replies has a level above the fast frontier's 256 nodes
+    assert (got["front"][c["live"]][:, c["ks"]][big] > 256).all()
 
 
 def test_nodoubles_takes_the_15_roll_mean(hc, case):
