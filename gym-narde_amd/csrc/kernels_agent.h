@@ -338,21 +338,9 @@ __global__ void __launch_bounds__(kBlock) k_mask576_move2(Planes pl, int n, Rng 
 // [0, 576) whatever the caller's buffer holds
 __device__ __forceinline__ int64_t clamp_code(int64_t c) { return c < 0 ? 0 : (c > 575 ? 575 : c); }
 
-// torch.argmax's order for (value, code) candidates: a NaN beats every
-// number (the lowest code among NaNs), else the larger value, the lower
-// code on ties; oi < 0 is "no candidate"
-__device__ __forceinline__ bool argmax_takes(float ov, int oi, float best, int bi) {
-  if (oi < 0) return false;
-  if (bi < 0) return true;
-  const bool on = __builtin_isnan(ov), bn = __builtin_isnan(best);
-  if (on || bn) return on && (!bn || oi < bi);
-  return ov > best || (ov == best && oi < bi);
-}
-
-__host__ __device__ inline uint64_t eps_to_q32(float epsilon) {
-  const double e = epsilon <= 0.0f ? 0.0 : (epsilon >= 1.0f ? 1.0 : (double)epsilon);
-  return (uint64_t)(e * 4294967296.0);
-}
+// (argmax_takes, the candidates' order, and eps_to_q32, the explore
+// threshold, are narde_rules.h's: the host check of the value rollout runs
+// them too)
 
 // the roll of env i for the play-set kernels: given (roll order) or the
 // next step's device dice; false for a given die outside 1..6 (no play)

@@ -24,6 +24,8 @@
 //                       (k_aft_count, k_aft_fill, k_aft_fill_scored)
 //   kernels_lookahead.h  REF2 two-ply lookahead: the record fill and the
 //                       expected-best-reply pass (k_aft_fill_rec, k_aft_look)
+//   kernels_value_rollout.h  REF2 value-greedy games in one launch, a net per
+//                       colour (k_value_rollout)
 //   kernels_turn_afterstates.h  FULL4 whole-turn afterstates: the level walk
 //                       (k_turn_count, k_turn_fill, k_turn_overflow, and the
 //                       scored fills)
@@ -60,6 +62,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_rows.h"
 #include "kernels_afterstates.h"
 #include "kernels_lookahead.h"
+#include "kernels_value_rollout.h"
 #include "kernels_turn_afterstates.h"
 #include "kernels_turn_lookahead.h"
 #include "kernels_td.h"
@@ -194,19 +197,7 @@ int check_expand(const narde_env* e, int64_t cap, const int32_t* offsets, int ma
 // narde_turn_afterstates_scored) checks of the net, and the kernels' view of it.
 int check_value_net(const narde_value_mlp* net, int perspective, float* value, ValNet& vn) {
   if (!net || !value) return fail(NARDE_EINVAL, "NULL argument");
-  if (!net->w1t || !net->b1 || !net->w2 || !net->b2) return fail(NARDE_EINVAL, "the net has a NULL weight array");
-  if (net->hidden < 1 || net->hidden > NARDE_VALUE_HIDDEN_MAX)
-    return fail(NARDE_EINVAL, "hidden %d outside 1..%d", (int)net->hidden, NARDE_VALUE_HIDDEN_MAX);
-  if (net->ld_w1t < net->hidden || net->ld_w1t > kValLdMax)
-    return fail(NARDE_EINVAL, "ld_w1t %lld outside hidden %d .. %lld", (long long)net->ld_w1t, (int)net->hidden,
-                (long long)kValLdMax);
-  if (net->hidden_act < 0 || net->hidden_act > 2 || net->out_act < 0 || net->out_act > 2)
-    return fail(NARDE_EINVAL, "activations: hidden 0 sigmoid, 1 tanh, 2 relu; out 0 none, 1 sigmoid, 2 tanh");
-  if (perspective != 0 && perspective != 1)
-    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
-  vn = ValNet{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act, net->out_act,
-              perspective, value};
-  return NARDE_OK;
+  return check_value_mlp(net, perspective, value, kValLdMax, vn);
 }
 
 // narde_value_td_trace's and narde_value_td_apply's checks of the net and the
@@ -215,15 +206,10 @@ static_assert(kTdSlab == NARDE_TD_SLAB, "narde.h and narde_rules.h state the sam
 int check_td(const narde_env* e, const narde_value_mlp_train* net, const float* trace, int64_t ld_trace,
              const float* v, const uint8_t* black, TdNet& tn) {
   if (!e || !net || !trace || !v || !black) return fail(NARDE_EINVAL, "NULL argument");
-  if (!net->w1t || !net->b1 || !net->w2 || !net->b2) return fail(NARDE_EINVAL, "the net has a NULL weight array");
-  if (net->hidden < 1 || net->hidden > NARDE_VALUE_HIDDEN_MAX)
-    return fail(NARDE_EINVAL, "hidden %d outside 1..%d", (int)net->hidden, NARDE_VALUE_HIDDEN_MAX);
-  if (net->ld_w1t < net->hidden || net->ld_w1t > kValLdMax)
-    return fail(NARDE_EINVAL, "ld_w1t %lld outside hidden %d .. %lld", (long long)net->ld_w1t, (int)net->hidden,
-                (long long)kValLdMax);
+  if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
+                                      net->out_act, kValLdMax))
+    return rc;
   if (net->w1 && net->ld_w1 < 198) return fail(NARDE_EINVAL, "ld_w1 %lld below 198", (long long)net->ld_w1);
-  if (net->hidden_act < 0 || net->hidden_act > 2 || net->out_act < 0 || net->out_act > 2)
-    return fail(NARDE_EINVAL, "activations: hidden 0 sigmoid, 1 tanh, 2 relu; out 0 none, 1 sigmoid, 2 tanh");
   const int64_t P = td_row_floats(net->hidden);
   if (ld_trace < P || (ld_trace & 3))
     return fail(NARDE_EINVAL, "ld_trace %lld: a multiple of 4, at least 200 x hidden + 1 = %lld", (long long)ld_trace,
@@ -781,6 +767,29 @@ int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* c
   // a row's two codes are one 32-bit word; no row: (0, 0)
   return pick_rows<uint32_t, 0>(e, offsets, codes, cap, value, ld_value, perspective, epsilon, seed, tag, actions,
                                  row, stream, "k_aft_pick", "codes and actions must be 4-B aligned");
+}
+
+int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
+                        const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice, int16_t* actions,
+                        float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+  if (!e) return fail(NARDE_EINVAL, "NULL handle");
+  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  if (!net_white && !net_black)
+    return fail(NARDE_EINVAL, "no net for either colour: random play against itself is narde_selfplay");
+  if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
+  if (reinterpret_cast<uintptr_t>(actions) % 4) return fail(NARDE_EINVAL, "actions must be 4-B aligned");
+  // (the kernel stores no per-row value: a net's value pointer stays NULL)
+  ValNet vw{}, vb{};
+  if (net_white)
+    if (const int rc = check_value_mlp(net_white, 1, nullptr, kValLdMax, vw)) return rc;
+  if (net_black)
+    if (const int rc = check_value_mlp(net_black, 1, nullptr, kValLdMax, vb)) return rc;
+  DeviceGuard dg(e->device);
+  const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
+                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated};
+  k_value_rollout<<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                   net_black != nullptr);
+  return check_launch("k_value_rollout");
 }
 
 int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,

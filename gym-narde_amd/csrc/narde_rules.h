@@ -2679,4 +2679,49 @@ NARDE_FN uint32_t turn_child(uint32_t path, int level, uint32_t w0, uint32_t w1,
   return turn_child_path(path, level, src, level == 0 && second);
 }
 
+// ------------------------------------------------- picks (DESIGN.md sections 13 and 19)
+// torch.argmax's order for (value, code) candidates: a NaN beats every
+// number (the lowest code among NaNs), else the larger value, the lower
+// code on ties; oi < 0 is "no candidate".  A total order: the best of a set
+// does not depend on the order the candidates are offered in.
+NARDE_FN bool argmax_takes(float ov, int oi, float best, int bi) {
+  if (oi < 0) return false;
+  if (bi < 0) return true;
+  const bool on = __builtin_isnan(ov), bn = __builtin_isnan(best);
+  if (on || bn) return on && (!bn || oi < bi);
+  return ov > best || (ov == best && oi < bi);
+}
+
+NARDE_FN uint64_t eps_to_q32(float epsilon) {
+  const double e = epsilon <= 0.0f ? 0.0 : (epsilon >= 1.0f ? 1.0 : (double)epsilon);
+  return (uint64_t)(e * 4294967296.0);
+}
+
+// the explore draw of env `env` under the tag `tag` (kernels_rows.h
+// aft_pick_row's): true if it fires; r1 picks the row, mulhi(r1, count)
+NARDE_FN bool explore_draw(uint32_t tag, uint32_t env, uint32_t k0, uint32_t k1, uint64_t eps_q32, uint32_t& r1) {
+  uint32_t r[4];
+  philox4x32_10(tag, env, 0u, 5u, k0, k1, r);
+  r1 = r[1];
+  return (uint64_t)r[0] < eps_q32;
+}
+
+// The value rollout's best row so far (kernels_value_rollout.h): x, what
+// aft_pick_row compares -- white's value v, negated when black moves --, the
+// row's ordinal among the env's rows and its two codes (code1 | code2 << 16).
+// ord < 0: none yet.
+struct RowBest {
+  float x, v;
+  int ord;
+  uint32_t codes;
+};
+NARDE_FN RowBest row_best_none() { return RowBest{0.0f, 0.0f, -1, 0u}; }
+NARDE_FN void row_best_merge(RowBest& b, const RowBest& o) {
+  if (argmax_takes(o.x, o.ord, b.x, b.ord)) b = o;
+}
+NARDE_FN void row_best_offer(RowBest& b, float v, int ord, uint32_t codes, bool smallest) {
+  row_best_merge(b, RowBest{smallest ? -v : v, v, ord, codes});
+}
+NARDE_FN uint32_t pack_codes(int c1, int c2) { return (uint32_t)(uint16_t)c1 | ((uint32_t)(uint16_t)c2 << 16); }
+
 }  // namespace narde

@@ -107,6 +107,8 @@ SIGNATURES = {
                                              _vp]),
     "narde_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp,
                                            _i64, _vp]),
+    "narde_value_rollout": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
                                                 _vp, _i64, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),

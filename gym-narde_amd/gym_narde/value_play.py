@@ -15,6 +15,8 @@ With a value_net.ValueMLP the rows are scored inside the expansion
 opponent's rolls, of the opponent's best reply under the same net);
 LookaheadPlayer is that search for either rule set
 (lookahead_turn_afterstates() on a rules="full4" env).
+play_match() answers "is net A better than net B, or than random play?":
+whole games in one launch a colour assignment (VecNardeEnv.value_rollout()).
 """
 
 
@@ -113,3 +115,34 @@ class LookaheadPlayer(ValuePlayer):
         super().__init__(env, net, perspective="white", fused=True, cap=cap, plies=1)
         self.plies = 2
         self._lookahead = env.lookahead_turn_afterstates if env.full else env.lookahead_afterstates
+
+
+def play_match(env, net_a, net_b, plies, epsilon=None, seed=0):
+    """net_a against net_b (value_net.ValueMLPs on the env's device; net_b
+    None: the random-legal policy, the baseline) on a rules="ref2" env, every
+    env playing with both colour assignments: env.reset() and one
+    value_rollout() launch of `plies` plies with a as white and b as black,
+    then env.reset() and one with the colours swapped.  Games that finish
+    inside a launch count, those still running at its end do not; envs
+    auto-reset, so one env plays several games.  A game the TimeLimit
+    truncates counts as a game and gives neither side points.  epsilon: both
+    sides explore with it (ply k of either launch under the tag k).
+    Returns {"games", "points_a", "points_b", "by_colour"}: the totals over
+    both launches, and by_colour = {"a_white": {"games", "points_a",
+    "points_b"}, "a_black": {...}} from env.stats() after each launch."""
+    if env.full:
+        raise ValueError('play_match() is rules="ref2" only')
+    if net_a is None:
+        raise ValueError("net_a is the net under test; pass None as net_b for the random baseline")
+    by = {}
+    none = dict(dice=False, actions=False, value=False, reward=False, terminated=False, truncated=False)
+    bufs = env.value_rollout_buffers(plies, **none)
+    tag = None if epsilon is None else 0
+    for name, white, black in (("a_white", net_a, net_b), ("a_black", net_b, net_a)):
+        env.reset()
+        env.value_rollout(plies, white, black, epsilon=epsilon, tag=tag, seed=seed, bufs=bufs)
+        games, pw, pb = (int(x) for x in env.stats().sum(0).tolist())
+        pa, pbb = (pw, pb) if name == "a_white" else (pb, pw)
+        by[name] = {"games": games, "points_a": pa, "points_b": pbb}
+    return {"games": sum(v["games"] for v in by.values()), "points_a": sum(v["points_a"] for v in by.values()),
+            "points_b": sum(v["points_b"] for v in by.values()), "by_colour": by}

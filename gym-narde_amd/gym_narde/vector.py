@@ -131,6 +131,9 @@ _FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAftersta
                        _lib.turn_lookahead_scratch_bytes)
 
 
+_SAME = object()  # value_rollout(): "net_black is net_white"
+
+
 class VecNardeEnv:
     def __init__(self, num_envs, device=None, seed=0, env_id_offset=0, dice_mode="all36",
                  max_episode_steps=1000, autoreset=True, rules="ref2"):
@@ -665,6 +668,82 @@ class VecNardeEnv:
                          _lib.ptr(bufs["obs"]), _lib.ptr(bufs["reward"]),
                          _lib.ptr(bufs["terminated"]), _lib.ptr(bufs["truncated"]),
                          _lib.ptr(bufs["legal"]), _lib.ptr(bufs["actions"]), self._s())
+        return bufs
+
+    def value_rollout_buffers(self, plies, dice=True, actions=True, value=True, reward=True, terminated=True,
+                              truncated=True):
+        """Allocate value_rollout()'s [plies][B] buffers: dice (plies,B,2)
+        uint8, actions (plies,B,2) int16, value (plies,B) float32, reward
+        (plies,B) int32, terminated / truncated (plies,B) uint8; None for
+        one switched off."""
+        t, B, dev = self.torch, self.num_envs, self.device
+        plies = int(plies)
+        mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
+        return dict(dice=mk(dice, (plies, B, 2), t.uint8), actions=mk(actions, (plies, B, 2), t.int16),
+                    value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
+                    terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
+
+    _VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("actions", (2,), "int16"), ("value", (), "float32"),
+                           ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
+
+    def value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None):
+        """plies plies of value-greedy play in ONE launch, a net per colour
+        (narde_value_rollout): every ply is what
+        ValuePlayer.step() does on its fused path -- the next step's dice,
+        scored_afterstates() under the mover's net (perspective "white"),
+        pick_afterstate(epsilon, tag + k, seed) for ply k, step() with
+        auto-reset -- with no row or value written on the way.  net_white /
+        net_black: value_net.ValueMLPs on the env's device (net_black
+        defaults to net_white); None for one colour makes that colour play
+        the random-legal policy, bit for bit step()'s own.  epsilon (f32) /
+        tag (int64): device scalars or numbers, together or not at all.
+        Returns bufs (value_rollout_buffers(): made when not given; an entry
+        None is not written): dice, actions, value -- white's value of the row
+        played, NaN on a random ply and where there was no row --, reward,
+        terminated, truncated, each [plies][B].  Statistics and the ply
+        counter advance as in step().  No synchronise; graph-safe when bufs,
+        epsilon and tag are given as device tensors (the weights are read
+        through pointers: call net.pack() after changing them)."""
+        if self.full:
+            raise ValueError('value_rollout() is rules="ref2" only')
+        t, B = self.torch, self.num_envs
+        plies = int(plies)
+        if plies < 1:
+            raise ValueError("plies must be >= 1")
+        if net_black is _SAME:
+            net_black = net_white
+        if net_white is None and net_black is None:
+            raise ValueError("a net for at least one colour (random play on both sides is selfplay())")
+        structs = []
+        for net in (net_white, net_black):
+            if net is None:
+                structs.append(None)
+                continue
+            if not hasattr(net, "struct"):
+                raise TypeError("net must be a gym_narde.value_net.ValueMLP")
+            mlp = net.struct()
+            if net.l1.weight.device != self.device:
+                raise ValueError("the net must live on the env's device")
+            structs.append(mlp)
+        if (epsilon is None) != (tag is None):
+            raise ValueError("epsilon and tag go together")
+        if epsilon is not None:
+            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
+            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+        if bufs is None:
+            bufs = self.value_rollout_buffers(plies)
+        for name, shape, dt in self._VALUE_ROLLOUT_BUFS:
+            a = bufs.get(name)
+            if a is None:
+                continue
+            if (a.dtype != getattr(t, dt) or a.device != self.device or not a.is_contiguous()
+                    or a.dim() != 2 + len(shape) or a.shape[0] < plies or tuple(a.shape[1:]) != (B,) + shape):
+                raise ValueError(f"bufs[{name!r}] must be a contiguous {dt} device tensor of shape "
+                                 f"(>= {plies}, {B}{''.join(f', {k}' for k in shape)})")
+        self.handle.call("narde_value_rollout", plies, *(ctypes.byref(m) if m is not None else None for m in structs),
+                         _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
+                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS), self._s())
+        self._keep = (net_white, net_black, structs, epsilon, tag, bufs)
         return bufs
 
     def rollout_launcher(self, plies, bufs, events=None, totals=None):

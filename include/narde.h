@@ -458,6 +458,39 @@ int narde_afterstates_lookahead(narde_env *env, const uint8_t *dice, int64_t cap
                                 const narde_value_mlp *net, int perspective, float *value,
                                 void *scratch, int64_t scratch_bytes, void *stream);
 
+/* Whole value-greedy games in one launch, one net per colour (REF2; DESIGN.md
+ * section 19).  For k = 0 .. plies - 1 every env e does what these three
+ * calls do:
+ *   narde_afterstates_scored(dice = NULL, the net of e's mover, perspective 1);
+ *   narde_afterstate_pick(perspective 1, epsilon, seed, tag = *tag + k) -- the
+ *     same tie rule (the lowest row), NaN rule (the first NaN) and explore
+ *     draw Philox4x32-10({*tag + k, e, 0, 5}, seed); epsilon NULL: greedy;
+ *   narde_step(those actions, dice = NULL, autoreset = 1).
+ * An env with no row steps with (0, 0) -- a pass, with
+ * narde_afterstates_lookahead's one exception (the bear-off from point 0).
+ * The mover's net is net_black when black moves, net_white otherwise; they
+ * may be the same struct.  A NULL net makes that colour's plies the
+ * random-legal policy's: bit for bit narde_step(actions = NULL, dice = NULL,
+ * autoreset = 1), drawn from the same words of the ply stream.  Both NULL is
+ * NARDE_EINVAL (that is narde_selfplay).
+ * Outputs, each optional, laid out [plies][B]: dice u8[2] the roll used,
+ * actions i16[2] the codes played, value f32 white's value of the picked row
+ * (a terminal row's: its outcome; NaN on a random ply and on a ply with no
+ * row), reward / terminated / truncated as narde_step gives them.  The
+ * statistics accumulate as in narde_step and t advances by plies.  No row,
+ * feature or per-row value goes to memory; the same inputs give the same bits.
+ * The handle has no rule set of its own: the plies are REF2's (on a
+ * rules = "full4" env the Python calls raise).
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable (one
+ * kernel node; epsilon and tag are read on the device).  NARDE_EINVAL before
+ * any device call: a NULL handle, narde_afterstates_scored's net errors for
+ * either net, plies < 1, epsilon and tag not both set or both NULL, actions
+ * not 4-B aligned. */
+int narde_value_rollout(narde_env *env, int plies, const narde_value_mlp *net_white,
+                        const narde_value_mlp *net_black, const float *epsilon, uint64_t seed,
+                        const int64_t *tag, uint8_t *dice, int16_t *actions, float *value,
+                        int32_t *reward, uint8_t *terminated, uint8_t *truncated, void *stream);
+
 /* narde_afterstates_scored over narde_turn_afterstates' rows (FULL4), the overflow path
  * included; that call's workspace rule holds (the handle's first call of
  * either, outside capture). */
