@@ -5,8 +5,11 @@ env plays whole games with A as white and B as black, then with the colours
 swapped, each colour assignment one launch on the GPU
 (gym_narde.value_play.play_match over VecNardeEnv.value_rollout; DESIGN.md
 section 19).  Without --b the opponent is the random-legal policy.
+--rules full4: whole turns under the real rules, for nets trained with
+train_value_agent.py --rules full4 (play_turn_match over turn_value_rollout;
+DESIGN.md section 20).
 
-  python examples/eval_value_agents.py --a FILE [--b FILE] [--envs B] [--plies N] [--seed S] [--out-act none|sigmoid|tanh]
+  python examples/eval_value_agents.py --a FILE [--b FILE] [--envs B] [--plies N] [--seed S] [--out-act none|sigmoid|tanh] [--rules ref2|full4]
 """
 import argparse
 import os
@@ -26,14 +29,14 @@ def load_net(path, out_act, device):
     return net.eval()
 
 
-def main(a, b=None, envs=1024, plies=400, seed=0, out_act="tanh", device="cuda"):
-    from gym_narde.value_play import play_match
+def main(a, b=None, envs=1024, plies=400, seed=0, out_act="tanh", device="cuda", rules="ref2"):
+    from gym_narde.value_play import play_match, play_turn_match
     from gym_narde.vector import VecNardeEnv
 
-    env = VecNardeEnv(envs, device=device, seed=seed)
+    env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
     net_a = load_net(a, out_act, env.device)
     net_b = load_net(b, out_act, env.device) if b else None
-    res = play_match(env, net_a, net_b, plies, seed=seed)
+    res = (play_turn_match if env.full else play_match)(env, net_a, net_b, plies, seed=seed)
     who = os.path.basename(b) if b else "random play"
     print(f"{os.path.basename(a)} against {who}: {envs} envs x {plies} plies a colour assignment, "
           f"{res['games']} games finished, points a {res['points_a']} / b {res['points_b']}")
@@ -51,5 +54,6 @@ if __name__ == "__main__":
     ap.add_argument("--plies", type=int, default=400)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out-act", choices=("none", "sigmoid", "tanh"), default="tanh")
+    ap.add_argument("--rules", choices=("ref2", "full4"), default="ref2")
     x = ap.parse_args()
-    main(x.a, x.b, x.envs, x.plies, x.seed, x.out_act)
+    main(x.a, x.b, x.envs, x.plies, x.seed, x.out_act, rules=x.rules)

@@ -14,8 +14,9 @@ search -- every afterstate is valued by the expectation, over the opponent's
 rolls, of the opponent's best reply under the same net (value_play's
 LookaheadPlayer: lookahead_afterstates, --rules full4:
 lookahead_turn_afterstates over whole-turn replies; --plies is already the
-number of plies played).  --one-launch (ref2, depth 1; implies --fused): the
---plies plies are one launch (VecNardeEnv.value_rollout), the same games.
+number of plies played).  --one-launch (depth 1; implies --fused): the
+--plies plies are one launch (VecNardeEnv.value_rollout, --rules full4:
+turn_value_rollout), the same games.
 
   python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2] [--one-launch]
 """
@@ -53,8 +54,8 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
             hidden = sd["0.weight"].shape[0]
             net[0], net[2] = torch.nn.Linear(198, hidden).to(env.device), torch.nn.Linear(hidden, 1).to(env.device)
         net.load_state_dict(sd)
-    if one_launch and (rules != "ref2" or depth != 1):
-        raise ValueError("--one-launch is --rules ref2 --depth 1")
+    if one_launch and depth != 1:
+        raise ValueError("--one-launch is --depth 1")
     if fused or depth == 2 or one_launch:
         from gym_narde.value_net import ValueMLP
 
@@ -62,7 +63,8 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
     player = LookaheadPlayer(env, net) if depth == 2 else ValuePlayer(env, net, perspective="white")
     eps = torch.tensor(epsilon, dtype=torch.float32, device=env.device) if epsilon > 0 else None
     if one_launch:
-        env.value_rollout(plies, net, epsilon=eps, tag=None if eps is None else 0, seed=seed)
+        rollout = env.turn_value_rollout if env.full else env.value_rollout
+        rollout(plies, net, epsilon=eps, tag=None if eps is None else 0, seed=seed)
         ep, white, black = (int(x) for x in env.stats().sum(0).tolist())
         print(f"{envs} envs x {plies} plies in one launch: {ep} games finished, points white {white} / black {black}")
         env.close()
@@ -91,7 +93,7 @@ if __name__ == "__main__":
     ap.add_argument("--depth", type=int, choices=(1, 2), default=1,
                     help="2: value every afterstate by the opponent's expected best reply (ref2 and full4)")
     ap.add_argument("--one-launch", action="store_true",
-                    help="play the plies in one launch (value_rollout; ref2, depth 1)")
+                    help="play the plies in one launch (value_rollout, full4: turn_value_rollout; depth 1)")
     a = ap.parse_args()
     main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused, depth=a.depth,
          one_launch=a.one_launch)

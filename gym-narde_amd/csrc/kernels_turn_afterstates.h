@@ -101,6 +101,22 @@ struct TurnLook {
 __device__ __forceinline__ float turn_look_level(const Side& s, const TurnRoot& r, const uint32_t* pcur, int nrows,
                                                  int level, const ValNet& vn, ValStage& VS, const TurnLook& lk, int lane);
 
+// The picking consumer (kernels_turn_value_rollout.h): the walk starts from
+// the position and the roll as the reducing consumer's does (vr is not used:
+// the root forward runs behind the walk, once the roll is known to have a
+// row); the final level is scored against the position and narde_turn_pick's
+// row kept -- its ordinal in the level, white's value of it and, in
+// RowBest's payload, its path word -- or, explore, the one row of ordinal
+// mulhi(r1, nrows).  level, dh, dl: what turn_path_play needs of the walk.
+struct TurnPick : TurnLook {
+  bool explore;
+  uint32_t r1;
+  RowBest b;
+  int level, dh, dl;
+};
+__device__ __forceinline__ void turn_pick_level(const Side& s, const TurnRoot& r, const uint32_t* pcur, int nrows,
+                                                int level, const ValNet& vn, ValStage& VS, TurnPick& pk, int lane);
+
 // the position a walk starts from: env e's record, or the reducing consumer's
 template <bool kLook>
 __device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const TurnLook* lk) {
@@ -125,7 +141,8 @@ __device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const Tu
 // (kernels_rows.h "the scored rows"; VS the wave's lists).  kRec (a fill
 // with a.feat NULL): the rows' records to *tr as well.  kLook (no fill): the
 // rows' values under vn against lk->vr reduced to the replier's best, left in
-// lk->best.
+// lk->best.  kPick (with kLook; lk is a TurnPick): the best row and its path
+// kept in place of the reduction.
 // (The walk and its consumers are one function on purpose, and the existing
 // instantiations compile to the instructions they had: with the walk a
 // function of its own that hands the final level to its callers -- by
@@ -133,7 +150,7 @@ __device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const Tu
 // wrapper -- k_turn_overflow_scored ran 2 to 7 % and k_turn_fill_scored up to
 // 2 % slower than before, outside the runs' spread; DESIGN.md section 18.2,
 // MEASUREMENT_LOG M.34.)
-template <bool kFill, bool kScore = false, bool kRec = false, bool kLook = false>
+template <bool kFill, bool kScore = false, bool kRec = false, bool kLook = false, bool kPick = false>
 __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt, uint32_t* pathA, uint32_t* pathB,
                                         int room, TurnScan& L, AftStage* S, const ValNet* vn = nullptr,
                                         ValStage* VS = nullptr, const TurnRec* tr = nullptr, TurnLook* lk = nullptr) {
@@ -276,7 +293,8 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
       if constexpr (kScore) val_score_rows(*vn, *VS, vr, a.cap, row0 + g0, min(64, nrows - g0), lane);
     }
   }
-  if constexpr (kLook) lk->best = turn_look_level(s, r, pcur, nrows, level, *vn, *VS, *lk, lane);
+  if constexpr (kLook && !kPick) lk->best = turn_look_level(s, r, pcur, nrows, level, *vn, *VS, *lk, lane);
+  if constexpr (kPick) turn_pick_level(s, r, pcur, nrows, level, *vn, *VS, *static_cast<TurnPick*>(lk), lane);
   return nrows;
 }
 

@@ -33,6 +33,9 @@
 //                       reply walk per (row, roll), its overflow pass and the
 //                       mean (k_turn_fill_rec, k_turn_look, k_turn_look_overflow,
 //                       k_turn_look_mean)
+//   kernels_turn_value_rollout.h  FULL4 value-greedy games in one launch: the
+//                       picking consumer of the level walk inside a ply loop
+//                       (k_turn_value_rollout)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
 // This file keeps the handle, the host-side checks and every C entry point.
@@ -65,6 +68,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_value_rollout.h"
 #include "kernels_turn_afterstates.h"
 #include "kernels_turn_lookahead.h"
+#include "kernels_turn_value_rollout.h"
 #include "kernels_td.h"
 
 namespace {
@@ -769,27 +773,79 @@ int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* c
                                  row, stream, "k_aft_pick", "codes and actions must be 4-B aligned");
 }
 
-int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
-                        const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice, int16_t* actions,
-                        float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+namespace {
+
+// The value rollouts' (narde_value_rollout, narde_turn_value_rollout) checks of
+// the plies, the explore pair, the action column (`align`-byte words;
+// misaligned: the error's text) and the two nets, and the kernels' view of the
+// nets (the kernels store no per-row value: a net's value pointer stays NULL)
+int check_rollout_nets(const narde_env* e, int plies, const narde_value_mlp* net_white,
+                       const narde_value_mlp* net_black, const float* epsilon, const int64_t* tag, const void* column,
+                       unsigned align, const char* misaligned, ValNet& vw, ValNet& vb) {
   if (!e) return fail(NARDE_EINVAL, "NULL handle");
   if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
   if (!net_white && !net_black)
     return fail(NARDE_EINVAL, "no net for either colour: random play against itself is narde_selfplay");
   if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
-  if (reinterpret_cast<uintptr_t>(actions) % 4) return fail(NARDE_EINVAL, "actions must be 4-B aligned");
-  // (the kernel stores no per-row value: a net's value pointer stays NULL)
-  ValNet vw{}, vb{};
+  if (reinterpret_cast<uintptr_t>(column) % align) return fail(NARDE_EINVAL, "%s", misaligned);
   if (net_white)
     if (const int rc = check_value_mlp(net_white, 1, nullptr, kValLdMax, vw)) return rc;
   if (net_black)
     if (const int rc = check_value_mlp(net_black, 1, nullptr, kValLdMax, vb)) return rc;
+  return NARDE_OK;
+}
+
+}  // namespace
+
+int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
+                        const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice, int16_t* actions,
+                        float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+  ValNet vw{}, vb{};
+  if (const int rc = check_rollout_nets(e, plies, net_white, net_black, epsilon, tag, actions, 4,
+                                        "actions must be 4-B aligned", vw, vb))
+    return rc;
   DeviceGuard dg(e->device);
   const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
                  (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated};
   k_value_rollout<<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
                                                                    net_black != nullptr);
   return check_launch("k_value_rollout");
+}
+
+int narde_turn_value_rollout_waves(const narde_env* e, int* waves) {
+  if (!e || !waves) return fail(NARDE_EINVAL, "NULL argument");
+  DeviceGuard dg(e->device);
+  hipDeviceProp_t prop;
+  int per_cu = 0;
+  hipError_t err = hipGetDeviceProperties(&prop, e->device);
+  if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_turn_value_rollout, 64, 0);
+  if (err != hipSuccess) return fail(NARDE_EHIP, "k_turn_value_rollout occupancy: %s", hipGetErrorString(err));
+  *waves = prop.multiProcessorCount * per_cu;
+  return NARDE_OK;
+}
+
+int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white,
+                             const narde_value_mlp* net_black, const float* epsilon, uint64_t seed, const int64_t* tag,
+                             uint8_t* dice, int8_t* play, float* value, int32_t* reward, uint8_t* terminated,
+                             uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* stream) {
+  ValNet vw{}, vb{};
+  if (const int rc = check_rollout_nets(e, plies, net_white, net_black, epsilon, tag, play, 8,
+                                        "play must be 8-B aligned", vw, vb))
+    return rc;
+  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
+  if (pieces < 1)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
+                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  DeviceGuard dg(e->device);
+  const int64_t waves = pieces < e->n ? pieces : e->n;
+  const TvrArgs a{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
+                  (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
+                  truncated, (uint8_t*)scratch};
+  k_turn_value_rollout<<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                         net_black != nullptr);
+  return check_launch("k_turn_value_rollout");
 }
 
 int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,

@@ -2636,6 +2636,22 @@ NARDE_FN uint64_t turn_path_play(uint32_t path, int n, int dh, int dl) {
   return pw;
 }
 
+// turn_path_play built as two 32-bit words (sub-moves 0, 1 and 2, 3): the
+// same play word.  For k_turn_value_rollout, where the level is a scalar of a
+// long loop and hipcc (ROCm 7.2) folded the 64-bit inserts' untouched upper
+// word to 0 -- a play of two sub-moves came out padded with 0 in place of -1.
+NARDE_FN uint64_t turn_path_play_words(uint32_t path, int n, int dh, int dl) {
+  uint32_t lo = ~0u, hi = ~0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint32_t v = ((uint32_t)turn_path_die(path, k, dh, dl) << 8) | (uint32_t)turn_path_from(path, k);
+    const int sh = 16 * (k & 1);
+    uint32_t& w = k < 2 ? lo : hi;
+    w = k < n ? ((w & ~(0xFFFFu << sh)) | (v << sh)) : w;
+  }
+  return (uint64_t)lo | ((uint64_t)hi << 32);
+}
+
 struct TurnRoot {
   uint32_t low;  // the block rule's low mask: the opponent is fixed for the turn
   int dh, dl;

@@ -38,6 +38,11 @@ def turn_lookahead_scratch_bytes(cap):
     return 128 * int(cap)
 
 
+def turn_rollout_scratch_bytes(waves):
+    """NARDE_TURN_ROLLOUT_SCRATCH_BYTES: narde_turn_value_rollout's scratch, a piece a wave."""
+    return 83536 * int(waves)
+
+
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
 
@@ -111,6 +116,9 @@ SIGNATURES = {
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
                                                 _vp, _i64, _vp]),
+    "narde_turn_value_rollout_waves": (_i32, [_vp, _vp]),
+    "narde_turn_value_rollout": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64, _vp,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

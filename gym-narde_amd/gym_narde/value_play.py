@@ -16,7 +16,9 @@ opponent's rolls, of the opponent's best reply under the same net);
 LookaheadPlayer is that search for either rule set
 (lookahead_turn_afterstates() on a rules="full4" env).
 play_match() answers "is net A better than net B, or than random play?":
-whole games in one launch a colour assignment (VecNardeEnv.value_rollout()).
+whole games in one launch a colour assignment (VecNardeEnv.value_rollout());
+play_turn_match() is the same on a rules="full4" env
+(VecNardeEnv.turn_value_rollout()).
 """
 
 
@@ -132,15 +134,30 @@ def play_match(env, net_a, net_b, plies, epsilon=None, seed=0):
     "points_b"}, "a_black": {...}} from env.stats() after each launch."""
     if env.full:
         raise ValueError('play_match() is rules="ref2" only')
+    return _match(env, env.value_rollout_buffers, "actions", env.value_rollout, net_a, net_b, plies, epsilon, seed)
+
+
+def play_turn_match(env, net_a, net_b, plies, epsilon=None, seed=0):
+    """play_match() on a rules="full4" env: whole turns, one
+    turn_value_rollout() launch of `plies` plies per colour assignment
+    (DESIGN.md section 20).  The same arguments and the same dictionary."""
+    if not env.full:
+        raise ValueError('play_turn_match() is rules="full4" only')
+    return _match(env, env.turn_value_rollout_buffers, "play", env.turn_value_rollout, net_a, net_b, plies, epsilon,
+                  seed)
+
+
+def _match(env, buffers, column, rollout, net_a, net_b, plies, epsilon, seed):
     if net_a is None:
         raise ValueError("net_a is the net under test; pass None as net_b for the random baseline")
     by = {}
-    none = dict(dice=False, actions=False, value=False, reward=False, terminated=False, truncated=False)
-    bufs = env.value_rollout_buffers(plies, **none)
+    none = dict(dice=False, value=False, reward=False, terminated=False, truncated=False)
+    none[column] = False
+    bufs = buffers(plies, **none)
     tag = None if epsilon is None else 0
     for name, white, black in (("a_white", net_a, net_b), ("a_black", net_b, net_a)):
         env.reset()
-        env.value_rollout(plies, white, black, epsilon=epsilon, tag=tag, seed=seed, bufs=bufs)
+        rollout(plies, white, black, epsilon=epsilon, tag=tag, seed=seed, bufs=bufs)
         games, pw, pb = (int(x) for x in env.stats().sum(0).tolist())
         pa, pbb = (pw, pb) if name == "a_white" else (pb, pw)
         by[name] = {"games": games, "points_a": pa, "points_b": pbb}

@@ -686,26 +686,9 @@ class VecNardeEnv:
     _VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("actions", (2,), "int16"), ("value", (), "float32"),
                            ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
 
-    def value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None):
-        """plies plies of value-greedy play in ONE launch, a net per colour
-        (narde_value_rollout; DESIGN.md section 19): every ply is what
-        ValuePlayer.step() does on its fused path -- the next step's dice,
-        scored_afterstates() under the mover's net (perspective "white"),
-        pick_afterstate(epsilon, tag + k, seed) for ply k, step() with
-        auto-reset -- with no row or value written on the way.  net_white /
-        net_black: value_net.ValueMLPs on the env's device (net_black
-        defaults to net_white); None for one colour makes that colour play
-        the random-legal policy, bit for bit step()'s own.  epsilon (f32) /
-        tag (int64): device scalars or numbers, together or not at all.
-        Returns bufs (value_rollout_buffers(): made when not given; an entry
-        None is not written): dice, actions, value -- white's value of the row
-        played, NaN on a random ply and where there was no row --, reward,
-        terminated, truncated, each [plies][B].  Statistics and the ply
-        counter advance as in step().  No synchronise; graph-safe when bufs,
-        epsilon and tag are given as device tensors (the weights are read
-        through pointers: call net.pack() after changing them)."""
-        if self.full:
-            raise ValueError('value_rollout() is rules="ref2" only')
+    def _value_rollout_args(self, plies, net_white, net_black, epsilon, tag, bufs, make_bufs, layout):
+        """value_rollout()'s and turn_value_rollout()'s argument checks: (plies,
+        net_white, net_black, the nets' structs, epsilon, tag, bufs)."""
         t, B = self.torch, self.num_envs
         plies = int(plies)
         if plies < 1:
@@ -731,8 +714,8 @@ class VecNardeEnv:
             epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
             tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
         if bufs is None:
-            bufs = self.value_rollout_buffers(plies)
-        for name, shape, dt in self._VALUE_ROLLOUT_BUFS:
+            bufs = make_bufs(plies)
+        for name, shape, dt in layout:
             a = bufs.get(name)
             if a is None:
                 continue
@@ -740,10 +723,111 @@ class VecNardeEnv:
                     or a.dim() != 2 + len(shape) or a.shape[0] < plies or tuple(a.shape[1:]) != (B,) + shape):
                 raise ValueError(f"bufs[{name!r}] must be a contiguous {dt} device tensor of shape "
                                  f"(>= {plies}, {B}{''.join(f', {k}' for k in shape)})")
+        return plies, net_white, net_black, structs, epsilon, tag, bufs
+
+    def value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None):
+        """plies plies of value-greedy play in ONE launch, a net per colour
+        (narde_value_rollout; DESIGN.md section 19): every ply is what
+        ValuePlayer.step() does on its fused path -- the next step's dice,
+        scored_afterstates() under the mover's net (perspective "white"),
+        pick_afterstate(epsilon, tag + k, seed) for ply k, step() with
+        auto-reset -- with no row or value written on the way.  net_white /
+        net_black: value_net.ValueMLPs on the env's device (net_black
+        defaults to net_white); None for one colour makes that colour play
+        the random-legal policy, bit for bit step()'s own.  epsilon (f32) /
+        tag (int64): device scalars or numbers, together or not at all.
+        Returns bufs (value_rollout_buffers(): made when not given; an entry
+        None is not written): dice, actions, value -- white's value of the row
+        played, NaN on a random ply and where there was no row --, reward,
+        terminated, truncated, each [plies][B].  Statistics and the ply
+        counter advance as in step().  No synchronise; graph-safe when bufs,
+        epsilon and tag are given as device tensors (the weights are read
+        through pointers: call net.pack() after changing them)."""
+        if self.full:
+            raise ValueError('value_rollout() is rules="ref2" only')
+        plies, net_white, net_black, structs, epsilon, tag, bufs = self._value_rollout_args(
+            plies, net_white, net_black, epsilon, tag, bufs, self.value_rollout_buffers, self._VALUE_ROLLOUT_BUFS)
         self.handle.call("narde_value_rollout", plies, *(ctypes.byref(m) if m is not None else None for m in structs),
                          _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
                          *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS), self._s())
         self._keep = (net_white, net_black, structs, epsilon, tag, bufs)
+        return bufs
+
+    def turn_value_rollout_buffers(self, plies, dice=True, play=True, value=True, reward=True, terminated=True,
+                                   truncated=True):
+        """Allocate turn_value_rollout()'s [plies][B] buffers:
+        value_rollout_buffers() with play (plies,B,4,2) int8 -- the (from,
+        die) sub-moves, -1 padded -- in place of actions."""
+        t, B, dev = self.torch, self.num_envs, self.device
+        plies = int(plies)
+        mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
+        return dict(dice=mk(dice, (plies, B, 2), t.uint8), play=mk(play, (plies, B, 4, 2), t.int8),
+                    value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
+                    terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
+
+    _TURN_VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("play", (4, 2), "int8"), ("value", (), "float32"),
+                                ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
+
+    def turn_value_rollout_waves(self):
+        """The waves the device keeps resident for turn_value_rollout()'s
+        kernel (narde_turn_value_rollout_waves; launches nothing)."""
+        w = ctypes.c_int(0)
+        self.handle.call("narde_turn_value_rollout_waves", ctypes.byref(w))
+        return w.value
+
+    def turn_value_rollout_scratch(self, waves=None):
+        """A scratch tensor for turn_value_rollout(): `waves` pieces
+        (default min(B, turn_value_rollout_waves())), uint8 on the env's
+        device."""
+        if waves is None:
+            waves = min(self.num_envs, self.turn_value_rollout_waves())
+        if int(waves) < 1:
+            raise ValueError("waves must be >= 1")
+        return self.torch.empty(_lib.turn_rollout_scratch_bytes(waves), dtype=self.torch.uint8, device=self.device)
+
+    def turn_value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None,
+                           scratch=None):
+        """rules="full4": value_rollout() over whole turns
+        (narde_turn_value_rollout).  Every ply is what
+        ValuePlayer.step() does on a FULL4 env -- the next step's dice,
+        scored_turn_afterstates() under the mover's net (perspective
+        "white"), pick_turn(epsilon, tag + k, seed) for ply k, step() with
+        that play and auto-reset -- with no row or value written on the way;
+        an env with no row passes.  The nets, epsilon, tag and seed are
+        value_rollout()'s; a colour with None plays the random-legal policy,
+        bit for bit step()'s own.
+        Returns bufs (turn_value_rollout_buffers(): made when not given; an
+        entry None is not written): dice, play (plies,B,4,2) int8, value --
+        white's value of the row played, NaN on a random ply and on a pass --,
+        reward, terminated, truncated.
+        scratch: a uint8 device tensor of whole pieces
+        (turn_value_rollout_scratch()); the launch has as many one-wave
+        workgroups as it has pieces, B at most, and gives the same bits
+        whatever their number.  Not given: allocated once at min(B, resident
+        waves) pieces and kept on the env -- a caller capturing a graph makes
+        its first call outside capture or passes its own.  No synchronise;
+        graph-safe when bufs, scratch, epsilon and tag are given as device
+        tensors."""
+        if not self.full:
+            raise ValueError('turn_value_rollout() is rules="full4" only')
+        t = self.torch
+        plies, net_white, net_black, structs, epsilon, tag, bufs = self._value_rollout_args(
+            plies, net_white, net_black, epsilon, tag, bufs, self.turn_value_rollout_buffers,
+            self._TURN_VALUE_ROLLOUT_BUFS)
+        if scratch is None:
+            if getattr(self, "_turn_rollout_scratch", None) is None:
+                self._turn_rollout_scratch = self.turn_value_rollout_scratch()
+            scratch = self._turn_rollout_scratch
+        elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
+              or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
+            raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
+                             f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
+        self.handle.call("narde_turn_value_rollout", plies,
+                         *(ctypes.byref(m) if m is not None else None for m in structs),
+                         _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
+                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
+                         _lib.ptr(scratch), int(scratch.numel()), self._s())
+        self._keep = (net_white, net_black, structs, epsilon, tag, bufs, scratch)
         return bufs
 
     def rollout_launcher(self, plies, bufs, events=None, totals=None):

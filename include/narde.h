@@ -545,6 +545,56 @@ int narde_turn_afterstates_lookahead(narde_env *env, const uint8_t *dice, int64_
                                      const narde_value_mlp *net, int perspective, float *value,
                                      void *scratch, int64_t scratch_bytes, void *stream);
 
+/* Whole value-greedy FULL4 games in one launch, one net per colour (DESIGN.md
+ * section 20): narde_value_rollout under FULL4's whole turns.  For k = 0 ..
+ * plies - 1 every env e does what these three calls do:
+ *   narde_turn_afterstates_scored(dice = NULL, the net of e's mover,
+ *     perspective 1);
+ *   narde_turn_pick(perspective 1, epsilon, seed, tag = *tag + k) -- the same
+ *     tie rule (the lowest row), NaN rule (the first NaN) and explore draw
+ *     Philox4x32-10({*tag + k, e, 0, 5}, seed), the explored row of ordinal
+ *     mulhi(r1, count); epsilon NULL: greedy;
+ *   narde_step_full(that play, dice = NULL, autoreset = 1).
+ * An env with no row steps with the all -1 play: a pass (FULL4 has no
+ * analogue of REF2's code-0 exception).  The mover's net is net_black when
+ * black moves, net_white otherwise; they may be the same struct.  A NULL net
+ * makes that colour's plies the random-legal policy's: bit for bit
+ * narde_step_full(play = NULL, dice = NULL, autoreset = 1), drawn from the
+ * same words of the ply stream.  Both NULL is NARDE_EINVAL (that is
+ * narde_selfplay).
+ * Outputs, each optional, laid out [plies][B]: dice u8[2] the roll used, play
+ * i8[4][2] the (from, die) sub-moves played, -1 padding -- a net's ply: exactly
+ * what narde_step_full would be given; a random ply: what it played --, 8-B
+ * aligned; value f32 white's value of the row played (a terminal row's: its
+ * outcome; NaN on a random ply and on a pass); reward / terminated / truncated
+ * as narde_step_full gives them.  The statistics accumulate as in
+ * narde_step_full and t advances by plies.  No row, feature or per-row value
+ * goes to memory.
+ * scratch: device memory, 16-B aligned, cut into pieces of
+ * NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) bytes, one a wave: the launch is
+ * min(B, scratch_bytes / that) one-wave workgroups, wave w playing envs w,
+ * w + waves, ..., each for all its plies (a static assignment: nothing spins,
+ * nothing is claimed with an atomic).  A wave walks a turn's levels with 256
+ * nodes a level on chip and, when a level outgrows that, again in its piece
+ * (NARDE_TURN_AFT_MAX nodes a level): exact for every position.  The same
+ * inputs give the same bits whatever scratch_bytes; the contents of scratch
+ * afterwards are unspecified.  narde_turn_value_rollout_waves gives the number
+ * of waves the device keeps resident for the kernel (launches nothing): more
+ * pieces than that buy nothing.  The handle's narde_turn_afterstates workspace
+ * is not needed.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable (one
+ * kernel node; epsilon and tag are read on the device).  NARDE_EINVAL before
+ * any device call: a NULL handle, narde_value_rollout's cases for either net,
+ * plies < 1, epsilon and tag not both set or both NULL, play not 8-B aligned,
+ * a NULL or misaligned scratch, scratch_bytes below one piece. */
+#define NARDE_TURN_ROLLOUT_SCRATCH_BYTES(waves) (83536 * (int64_t)(waves))
+int narde_turn_value_rollout_waves(const narde_env *env, int *waves);
+int narde_turn_value_rollout(narde_env *env, int plies, const narde_value_mlp *net_white,
+                             const narde_value_mlp *net_black, const float *epsilon, uint64_t seed,
+                             const int64_t *tag, uint8_t *dice, int8_t *play, float *value,
+                             int32_t *reward, uint8_t *terminated, uint8_t *truncated,
+                             void *scratch, int64_t scratch_bytes, void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
  * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
