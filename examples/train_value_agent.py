@@ -8,8 +8,14 @@ of it on the device.  The output is tanh by default:
 outcomes are +-1 and +-2 (white's points, negative when black wins), which a
 sigmoid cannot reach.
 
+--window K trains with gym_narde.td.WindowTDLambdaLearner instead (DESIGN.md
+section 21): K plies of self-play in one launch, then one update from the
+window with the weights held fixed over it -- truncated TD(lambda), no trace
+array; --plies is rounded up to whole windows.  The file written is the same.
+
   python examples/train_value_agent.py [--envs B] [--plies N] [--hidden H] [--alpha A] [--lam L] [--epsilon E]
                                        [--rules ref2|full4] [--out-act none|sigmoid|tanh] [--seed S] [--out FILE]
+                                       [--window K]
 
 Play the result:  python examples/play_value_agent.py --weights FILE --fused
 """
@@ -21,27 +27,32 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 
 def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rules="ref2", out_act="tanh", seed=0,
-         out="value_agent.pt", device="cuda", report=10):
+         out="value_agent.pt", device="cuda", report=10, window=0):
     import torch
 
-    from gym_narde.td import TDLambdaLearner
+    from gym_narde.td import TDLambdaLearner, WindowTDLambdaLearner
     from gym_narde.value_net import ValueMLP
     from gym_narde.vector import VecNardeEnv
 
     env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
     torch.manual_seed(seed)
     net = ValueMLP(hidden, "sigmoid", out_act).to(env.device)
-    learner = TDLambdaLearner(env, net, alpha=alpha, lam=lam, epsilon=epsilon, seed=seed)
+    if window:
+        learner = WindowTDLambdaLearner(env, net, alpha=alpha, lam=lam, plies=window, epsilon=epsilon, seed=seed)
+        steps, per = -(-plies // window), window
+    else:
+        learner = TDLambdaLearner(env, net, alpha=alpha, lam=lam, epsilon=epsilon, seed=seed)
+        steps, per = plies, 1
     print(f"{envs} envs, hidden {hidden}, out {out_act}: learner memory {learner.memory_bytes() / 1e6:.1f} MB")
-    every = max(1, plies // max(1, report))
+    every = max(1, steps // max(1, report))
     err = torch.zeros((), device=env.device)
-    for ply in range(plies):
+    for step in range(steps):
         delta = learner.step()[-1]
         err += delta.abs().mean()
-        if (ply + 1) % every == 0 or ply + 1 == plies:
-            n = (ply % every) + 1
+        if (step + 1) % every == 0 or step + 1 == steps:
+            n = (step % every) + 1
             ep = int(env.stats().sum(0)[0])
-            print(f"ply {ply + 1}: mean |delta| {float(err) / n:.4f}, {ep} games finished")
+            print(f"ply {(step + 1) * per}: mean |delta| {float(err) / n:.4f}, {ep} games finished")
             err.zero_()
     torch.save(net.state_dict(), out)
     print(f"saved {out}")
@@ -61,5 +72,6 @@ if __name__ == "__main__":
     ap.add_argument("--out-act", choices=("none", "sigmoid", "tanh"), default="tanh")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="value_agent.pt")
+    ap.add_argument("--window", type=int, default=0, help="K > 0: windowed TD(lambda), K plies a launch and update")
     a = ap.parse_args()
-    main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out)
+    main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out, window=a.window)

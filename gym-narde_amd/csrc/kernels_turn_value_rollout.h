@@ -46,6 +46,7 @@ struct TvrArgs {
   uint8_t* __restrict__ term;       // [plies][n]
   uint8_t* __restrict__ trunc;      // [plies][n]
   uint8_t* __restrict__ slab;       // [gridDim.x][kTurnSlabWave]
+  uint4* __restrict__ records;      // [plies][n][2]: the record each ply found (the kRec kernels only)
 };
 
 // The row the mover plays, of the final level a walk of s under r left
@@ -109,7 +110,8 @@ __device__ __forceinline__ int turn_pick_roll(TurnPick& pk, uint64_t* knxt, uint
 }
 
 // one-wave workgroups; wave w plays envs w, w + gridDim.x, ... (the LDS of
-// k_turn_look<1> and the carry)
+// k_turn_look<1> and the carry); kRec: a.records is written (vr_store_record)
+template <bool kRec>
 __global__ void __launch_bounds__(64) k_turn_value_rollout(TvrArgs a, ValNet net_w, ValNet net_b, int has_w,
                                                            int has_b) {
   __shared__ TurnFrontLds F;
@@ -130,6 +132,7 @@ __global__ void __launch_bounds__(64) k_turn_value_rollout(TvrArgs a, ValNet net
     wave_lds_handoff();  // (the last env's reads of the carry are done)
     if (lane == 0) C.st = make_int4(0, 0, 0, 0);
     for (int k = 0; k < a.plies; ++k) {
+      if (kRec && lane == 0) vr_store_record(a.records, (size_t)k * (size_t)a.n + (size_t)e, s);
       int d0, d1;
       {
         uint32_t R[4], r[4];

@@ -44,6 +44,7 @@ struct VrArgs {
   int32_t* __restrict__ reward;     // [plies][n]
   uint8_t* __restrict__ term;       // [plies][n]
   uint8_t* __restrict__ trunc;      // [plies][n]
+  uint4* __restrict__ records;      // [plies][n][2]: the record each ply found (the kRec kernels only)
 };
 
 struct alignas(16) VrStage {  // per wave: a chunk's kept rows' codes, by rank
@@ -138,7 +139,19 @@ __device__ __forceinline__ RowBest vr_choose(const Side& s, int d0, int d1, cons
   return b;
 }
 
-// one wave per env, an env per workgroup (k_aft_look<1>'s LDS and the codes)
+// ply k's record of env e as the ply found it, from lane 0 (the windowed TD
+// update's input): stored before the roll is applied,
+// so nothing of it is held across the expansion
+__device__ __forceinline__ void vr_store_record(uint4* __restrict__ records, size_t ix, const Side& s) {
+  uint4 ra, rb;
+  side_to_record(s, ra, rb);
+  records[2 * ix] = ra;
+  records[2 * ix + 1] = rb;
+}
+
+// one wave per env, an env per workgroup (k_aft_look<1>'s LDS and the codes);
+// kRec: a.records is written (the no-records instantiation holds no trace of it)
+template <bool kRec>
 __global__ void __launch_bounds__(64) k_value_rollout(VrArgs a, ValNet net_w, ValNet net_b, int has_w, int has_b) {
   __shared__ AftScan L;
   __shared__ ValStage VS;
@@ -152,6 +165,7 @@ __global__ void __launch_bounds__(64) k_value_rollout(VrArgs a, ValNet net_w, Va
   const uint32_t tag0 = a.eps ? (uint32_t)*a.tag : 0u;
   if (lane == 0) C.st = make_int4(0, 0, 0, 0);
   for (int k = 0; k < a.plies; ++k) {
+    if (kRec && lane == 0) vr_store_record(a.records, (size_t)k * (size_t)a.n + (size_t)e, s);
     int d0, d1;
     {
       uint32_t R[4], r[4];

@@ -43,6 +43,7 @@
 // host_common.h: the host helpers the two share.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstring>
 #include <initializer_list>
 #include <new>
@@ -70,6 +71,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_turn_lookahead.h"
 #include "kernels_turn_value_rollout.h"
 #include "kernels_td.h"
+#include "kernels_td_window.h"
 
 namespace {
 
@@ -797,19 +799,33 @@ int check_rollout_nets(const narde_env* e, int plies, const narde_value_mlp* net
 
 }  // namespace
 
-int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
-                        const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice, int16_t* actions,
-                        float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+int narde_value_rollout_records(narde_env* e, int plies, const narde_value_mlp* net_white,
+                                const narde_value_mlp* net_black, const float* epsilon, uint64_t seed,
+                                const int64_t* tag, uint8_t* dice, int16_t* actions, float* value, int32_t* reward,
+                                uint8_t* terminated, uint8_t* truncated, void* records, void* stream) {
   ValNet vw{}, vb{};
   if (const int rc = check_rollout_nets(e, plies, net_white, net_black, epsilon, tag, actions, 4,
                                         "actions must be 4-B aligned", vw, vb))
     return rc;
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
   const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
-                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated};
-  k_value_rollout<<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                   net_black != nullptr);
+                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated,
+                 (uint4*)records};
+  if (records)
+    k_value_rollout<true><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                           net_black != nullptr);
+  else
+    k_value_rollout<false><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                            net_black != nullptr);
   return check_launch("k_value_rollout");
+}
+
+int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
+                        const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice, int16_t* actions,
+                        float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* stream) {
+  return narde_value_rollout_records(e, plies, net_white, net_black, epsilon, seed, tag, dice, actions, value, reward,
+                                     terminated, truncated, nullptr, stream);
 }
 
 int narde_turn_value_rollout_waves(const narde_env* e, int* waves) {
@@ -818,16 +834,18 @@ int narde_turn_value_rollout_waves(const narde_env* e, int* waves) {
   hipDeviceProp_t prop;
   int per_cu = 0;
   hipError_t err = hipGetDeviceProperties(&prop, e->device);
-  if (err == hipSuccess) err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_turn_value_rollout, 64, 0);
+  if (err == hipSuccess)
+    err = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_turn_value_rollout<false>, 64, 0);
   if (err != hipSuccess) return fail(NARDE_EHIP, "k_turn_value_rollout occupancy: %s", hipGetErrorString(err));
   *waves = prop.multiProcessorCount * per_cu;
   return NARDE_OK;
 }
 
-int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white,
-                             const narde_value_mlp* net_black, const float* epsilon, uint64_t seed, const int64_t* tag,
-                             uint8_t* dice, int8_t* play, float* value, int32_t* reward, uint8_t* terminated,
-                             uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* stream) {
+int narde_turn_value_rollout_records(narde_env* e, int plies, const narde_value_mlp* net_white,
+                                     const narde_value_mlp* net_black, const float* epsilon, uint64_t seed,
+                                     const int64_t* tag, uint8_t* dice, int8_t* play, float* value, int32_t* reward,
+                                     uint8_t* terminated, uint8_t* truncated, void* scratch, int64_t scratch_bytes,
+                                     void* records, void* stream) {
   ValNet vw{}, vb{};
   if (const int rc = check_rollout_nets(e, plies, net_white, net_black, epsilon, tag, play, 8,
                                         "play must be 8-B aligned", vw, vb))
@@ -838,14 +856,27 @@ int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net
   if (pieces < 1)
     return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
                 (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
   const int64_t waves = pieces < e->n ? pieces : e->n;
   const TvrArgs a{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
                   (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
-                  truncated, (uint8_t*)scratch};
-  k_turn_value_rollout<<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                         net_black != nullptr);
+                  truncated, (uint8_t*)scratch, (uint4*)records};
+  if (records)
+    k_turn_value_rollout<true><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                                 net_black != nullptr);
+  else
+    k_turn_value_rollout<false><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                                  net_black != nullptr);
   return check_launch("k_turn_value_rollout");
+}
+
+int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white,
+                             const narde_value_mlp* net_black, const float* epsilon, uint64_t seed, const int64_t* tag,
+                             uint8_t* dice, int8_t* play, float* value, int32_t* reward, uint8_t* terminated,
+                             uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* stream) {
+  return narde_turn_value_rollout_records(e, plies, net_white, net_black, epsilon, seed, tag, dice, play, value, reward,
+                                          terminated, truncated, scratch, scratch_bytes, nullptr, stream);
 }
 
 int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
@@ -946,6 +977,57 @@ int narde_value_td_apply(narde_env* e, const narde_value_mlp_train* net, float* 
   if (const int rc = check_launch("k_td_partial")) return rc;
   k_td_update<<<(unsigned)((td_row_floats(tn.hidden) + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part,
                                                                                                    ld_part, slabs);
+  return check_launch("k_td_update");
+}
+
+int narde_value_td_window(narde_env* e, const narde_value_mlp_train* net, int plies, const void* records,
+                          const int32_t* reward, const uint8_t* terminated, const uint8_t* truncated, float alpha,
+                          float lam, float gamma, float* scratch, int64_t scratch_floats, float* delta, void* stream) {
+  if (!e || !net || !records || !reward || !terminated || !truncated || !scratch)
+    return fail(NARDE_EINVAL, "NULL argument");
+  if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
+                                      net->out_act, kValLdMax))
+    return rc;
+  if (net->w1 && net->ld_w1 < 198) return fail(NARDE_EINVAL, "ld_w1 %lld below 198", (long long)net->ld_w1);
+  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  if (((int64_t)plies + 1) * e->n >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "(plies + 1) x B = %lld samples: 2^31 or more", (long long)(((int64_t)plies + 1) * e->n));
+  if (!(lam >= 0.0f && lam <= 1.0f)) return fail(NARDE_EINVAL, "lam %g outside [0, 1]", (double)lam);
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  const int64_t need = tdw_scratch_floats(e->n, plies, net->hidden);
+  if (scratch_floats < need)
+    return fail(NARDE_EINVAL, "scratch_floats %lld below NARDE_TD_WINDOW_SCRATCH_FLOATS = %lld",
+                (long long)scratch_floats, (long long)need);
+  const TdNet tn{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->w1, net->ld_w1, net->hidden, net->hidden_act,
+                 net->out_act};
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  // k_tdw_grad's accumulator is past the 64 KB a launch may ask for unannounced from hidden = 82 on: once a device
+  static std::atomic<uint64_t> announced{0};
+  const uint64_t bit = uint64_t(1) << (e->device & 63);
+  if (!(announced.load(std::memory_order_relaxed) & bit)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tdw_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(td_row_floats(kValHiddenMax) * sizeof(float))));
+    announced.fetch_or(bit, std::memory_order_relaxed);
+  }
+  const int n = (int)e->n;
+  const int64_t stored = (int64_t)plies * n, all = stored + n;
+  const int slabs = (int)tdw_slabs(stored);
+  const int64_t P = td_row_floats(tn.hidden), ld_part = P + 3;
+  float* v = scratch;
+  float* G = v + tdw_round4(all);
+  float* part = G + tdw_round4(stored);
+  k_tdw_values<<<(unsigned)((all + kTdwWaves - 1) / kTdwWaves), kTdBlock, 0, st>>>(e->pl, (const uint4*)records, stored,
+                                                                                   all, tn, v);
+  if (const int rc = check_launch("k_tdw_values")) return rc;
+  k_tdw_returns<<<(unsigned)((n + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(
+      n, plies, (const uint32_t*)records, v, reward, terminated, truncated, gamma, gamma * lam, G, delta);
+  if (const int rc = check_launch("k_tdw_returns")) return rc;
+  k_tdw_grad<<<(unsigned)slabs, 2 * kTdBlock, (size_t)P * sizeof(float), st>>>((const uint4*)records, stored, tn, G, part,
+                                                                           ld_part);
+  if (const int rc = check_launch("k_tdw_grad")) return rc;
+  k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
   return check_launch("k_td_update");
 }
 

@@ -2321,6 +2321,32 @@ NARDE_FN float td_delta(bool terminated, bool truncated, int reward, uint32_t bl
   return target - v;
 }
 
+// ------------------------------------- windowed TD(lambda)
+// narde_value_td_window's arithmetic (kernels_td_window.h; the host check
+// tests/hostcheck/hostcheck_td_window.cpp runs the same functions in the
+// kernels' order).  A window is K plies of B envs, sample k B + e.
+constexpr int kTdwSlab = 128;  // samples a partial row of the gradient pass sums
+// G_k = delta_k + c_k G_{k+1}: c_k = 0 where ply k ended an episode, gamma lam
+// (gl) elsewhere; c_k = 0 gives delta_k's own bits
+NARDE_FN float td_return(float delta, bool ended, float gl, float g_next) {
+  return ended || gl == 0.0f ? delta : fmaf(gl, g_next, delta);
+}
+// The gradient pass's accumulator takes, per sample and in sample order, one
+// addend an element: G d_h x_c on the sample's own columns c < 198 and on b1's
+// (x = 1), G ga_h on w2's, G go on b2's (tdw_acc_b2).
+NARDE_FN float tdw_acc(float acc, float G, int c, float x, float d_h, float ga_h) {
+  return c == kTdColW2 ? fmaf(G, ga_h, acc) : fmaf(G * d_h, x, acc);
+}
+NARDE_FN float tdw_acc_b2(float acc, float G, float go) { return fmaf(G, go, acc); }
+// scratch: v [(K + 1) B], G [K B], each rounded up to whole float4s, then the
+// partial rows, td_row_floats + 3 floats each
+NARDE_FN int64_t tdw_round4(int64_t n) { return (n + 3) / 4 * 4; }
+NARDE_FN int64_t tdw_slabs(int64_t samples) { return (samples + kTdwSlab - 1) / kTdwSlab; }
+NARDE_FN int64_t tdw_scratch_floats(int64_t n, int plies, int hidden) {
+  return tdw_round4((int64_t)(plies + 1) * n) + tdw_round4((int64_t)plies * n) +
+         tdw_slabs((int64_t)plies * n) * (td_row_floats(hidden) + 3);
+}
+
 // ------------------------------------------------------------- Philox4x32-10
 NARDE_FN void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
                             uint32_t k1, uint32_t out[4]) {

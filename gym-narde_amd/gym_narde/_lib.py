@@ -14,6 +14,7 @@ OK = 0
 OFF = 24
 MAX_MOVES = 64
 TD_SLAB = 64  # NARDE_TD_SLAB
+TD_WINDOW_SLAB = 128  # NARDE_TD_WINDOW_SLAB
 TOTAL_ROWS = 64  # NARDE_TOTAL_ROWS
 
 
@@ -26,6 +27,13 @@ def td_scratch_floats(num_envs, hidden):
     """NARDE_TD_SCRATCH_FLOATS: narde_value_td_apply's scratch."""
     b = int(num_envs)
     return (b + 3) // 4 * 4 + (b + TD_SLAB - 1) // TD_SLAB * (200 * int(hidden) + 4)
+
+
+def td_window_scratch_floats(num_envs, plies, hidden):
+    """NARDE_TD_WINDOW_SCRATCH_FLOATS: narde_value_td_window's scratch."""
+    b, k = int(num_envs), int(plies)
+    return (((k + 1) * b + 3) // 4 * 4 + (k * b + 3) // 4 * 4
+            + (k * b + TD_WINDOW_SLAB - 1) // TD_WINDOW_SLAB * (200 * int(hidden) + 4))
 
 
 def lookahead_scratch_bytes(cap):
@@ -114,14 +122,20 @@ SIGNATURES = {
                                            _i64, _vp]),
     "narde_value_rollout": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_value_rollout_records": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64, _vp,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_afterstates_lookahead": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
                                                 _vp, _i64, _vp]),
     "narde_turn_value_rollout_waves": (_i32, [_vp, _vp]),
     "narde_turn_value_rollout": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "narde_turn_value_rollout_records": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64,
+                                                _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),
+    "narde_value_td_window": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

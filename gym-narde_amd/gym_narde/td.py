@@ -15,12 +15,111 @@ The kernels train net._w1t (what the scored expansions read) and the module's
 own parameters in place, l1.weight as the mirror of _w1t: net(feat),
 state_dict() and scored_afterstates(net) agree after every update and no
 pack() is needed.
+
+WindowTDLambdaLearner is the windowed form: K plies of
+self-play in one launch that writes each ply's record
+(narde_value_rollout_records / narde_turn_value_rollout_records), then one
+update from the window (narde_value_td_window) with the weights held fixed
+over it,
+    theta <- theta + alpha sum_e sum_k G_k grad_theta v(s_k),
+    G_k = delta_k + gamma lam G_{k+1} (cut where an episode ended, G_K = 0).
+It keeps no trace array.  It is truncated TD(lambda), not the online
+learner's algorithm: no credit crosses a window's left edge.
 """
 import ctypes
 
 from . import _lib
 from .value_net import HIDDEN_ACTS, OUT_ACTS
 from .value_play import ValuePlayer
+
+
+def _check_learner(name, env, net, lam):
+    if not (hasattr(net, "struct") and hasattr(net, "pack")):
+        raise TypeError(f"{name} needs a gym_narde.value_net.ValueMLP")
+    if not env.autoreset:
+        raise ValueError(f"{name} needs an env with autoreset=True")
+    if net.l1.weight.device != env.device:
+        raise ValueError(f"the net is on {net.l1.weight.device}, the env on {env.device}")
+    if not 0.0 <= float(lam) <= 1.0:
+        raise ValueError("lam must be in [0, 1]")
+
+
+def _train_struct(env, net):
+    """The ctypes narde_value_mlp_train over the net's live tensors."""
+    t = env.torch
+    net.struct()  # packs _w1t on first use, checks the parameters
+    w = net.l1.weight
+    if w.dtype != t.float32 or not w.is_contiguous():
+        raise ValueError("the learner needs a contiguous float32 l1.weight")
+    return _lib.ValueMlpTrain(net._w1t.data_ptr(), net.hidden, net.l1.bias.data_ptr(), net.l2.weight.data_ptr(),
+                              net.l2.bias.data_ptr(), net.hidden, HIDDEN_ACTS[net.hidden_act],
+                              OUT_ACTS[net.out_act], w.data_ptr(), w.stride(0))
+
+
+class WindowTDLambdaLearner:
+    """env: a VecNardeEnv (either rule set) with autoreset; net: a ValueMLP on
+    its device.  alpha: step size; lam: the return's decay; plies: the
+    window K; gamma: the discount; epsilon: the explore probability of the
+    play (None: greedy); seed: the explore draws' key."""
+
+    def __init__(self, env, net, alpha, lam, plies, gamma=1.0, epsilon=None, seed=0):
+        t = env.torch
+        _check_learner("WindowTDLambdaLearner", env, net, lam)
+        if int(plies) < 1:
+            raise ValueError("plies must be >= 1")
+        self.env, self.net, self.plies = env, net, int(plies)
+        self.alpha, self.lam, self.gamma, self.seed = float(alpha), float(lam), float(gamma), int(seed)
+        z = dict(device=env.device)
+        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
+        self.bufs = make(self.plies, records=True)
+        self.delta = t.zeros((self.plies, env.num_envs), dtype=t.float32, **z)
+        self.scratch = t.empty(_lib.td_window_scratch_floats(env.num_envs, self.plies, net.hidden), dtype=t.float32, **z)
+        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
+        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
+        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
+        self._mlp = _train_struct(env, net)
+
+    def play(self):
+        """The window's K plies in one launch, the net on both sides; the
+        explore tag advances by K.  Returns the launch's buffers."""
+        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
+        if env.full:
+            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
+        else:
+            env.value_rollout(self.plies, self.net, **kw)
+        if self._tag is not None:
+            self._tag += self.plies
+        return self.bufs
+
+    def update(self):
+        """One weight update from the window play() recorded."""
+        b = self.bufs
+        self.env.handle.call("narde_value_td_window", ctypes.byref(self._mlp), self.plies, _lib.ptr(b["records"]),
+                             _lib.ptr(b["reward"]), _lib.ptr(b["terminated"]), _lib.ptr(b["truncated"]), self.alpha,
+                             self.lam, self.gamma, _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.delta),
+                             self.env._s())
+
+    def step(self):
+        """K plies of self-play and their one update.  Returns (reward,
+        terminated, truncated, delta), each [plies][B] (the learner's own
+        buffers, rewritten by the next step)."""
+        b = self.play()
+        self.update()
+        return b["reward"], b["terminated"], b["truncated"], self.delta
+
+    def values(self):
+        """v (plies + 1, B) of the last update: v(s_k) under the weights it
+        found, the last row the envs' records as they stood (a view of the
+        scratch)."""
+        K, B = self.plies, self.env.num_envs
+        return self.scratch[:(K + 1) * B].view(K + 1, B)
+
+    def memory_bytes(self):
+        """Device memory the learner owns."""
+        own = [x for x in self.bufs.values() if x is not None] + [self.delta, self.scratch]
+        if self._roll_scratch is not None:
+            own.append(self._roll_scratch)
+        return sum(x.numel() * x.element_size() for x in own)
 
 
 class TDLambdaLearner:

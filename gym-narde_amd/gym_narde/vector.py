@@ -671,20 +671,26 @@ class VecNardeEnv:
         return bufs
 
     def value_rollout_buffers(self, plies, dice=True, actions=True, value=True, reward=True, terminated=True,
-                              truncated=True):
+                              truncated=True, records=False):
         """Allocate value_rollout()'s [plies][B] buffers: dice (plies,B,2)
         uint8, actions (plies,B,2) int16, value (plies,B) float32, reward
         (plies,B) int32, terminated / truncated (plies,B) uint8; None for
-        one switched off."""
+        one switched off.  records (off by default): (plies,B,8) int32, each
+        env's 32-byte record as the ply found it (what
+        td.WindowTDLambdaLearner trains on)."""
         t, B, dev = self.torch, self.num_envs, self.device
         plies = int(plies)
         mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
-        return dict(dice=mk(dice, (plies, B, 2), t.uint8), actions=mk(actions, (plies, B, 2), t.int16),
+        bufs = dict(dice=mk(dice, (plies, B, 2), t.uint8), actions=mk(actions, (plies, B, 2), t.int16),
                     value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
                     terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
+        if records:  # (the key exists only then: callers walk the dict)
+            bufs["records"] = t.empty((plies, B, 8), dtype=t.int32, device=dev)
+        return bufs
 
     _VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("actions", (2,), "int16"), ("value", (), "float32"),
                            ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
+    _RECORDS_BUF = ("records", (8,), "int32")
 
     def _value_rollout_args(self, plies, net_white, net_black, epsilon, tag, bufs, make_bufs, layout):
         """value_rollout()'s and turn_value_rollout()'s argument checks: (plies,
@@ -715,7 +721,7 @@ class VecNardeEnv:
             tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
         if bufs is None:
             bufs = make_bufs(plies)
-        for name, shape, dt in layout:
+        for name, shape, dt in layout + (self._RECORDS_BUF,):
             a = bufs.get(name)
             if a is None:
                 continue
@@ -739,7 +745,8 @@ class VecNardeEnv:
         Returns bufs (value_rollout_buffers(): made when not given; an entry
         None is not written): dice, actions, value -- white's value of the row
         played, NaN on a random ply and where there was no row --, reward,
-        terminated, truncated, each [plies][B].  Statistics and the ply
+        terminated, truncated, each [plies][B]; and, where bufs has it,
+        records (value_rollout_buffers(records=True)).  Statistics and the ply
         counter advance as in step().  No synchronise; graph-safe when bufs,
         epsilon and tag are given as device tensors (the weights are read
         through pointers: call net.pack() after changing them)."""
@@ -747,23 +754,28 @@ class VecNardeEnv:
             raise ValueError('value_rollout() is rules="ref2" only')
         plies, net_white, net_black, structs, epsilon, tag, bufs = self._value_rollout_args(
             plies, net_white, net_black, epsilon, tag, bufs, self.value_rollout_buffers, self._VALUE_ROLLOUT_BUFS)
-        self.handle.call("narde_value_rollout", plies, *(ctypes.byref(m) if m is not None else None for m in structs),
+        self.handle.call("narde_value_rollout_records", plies,
+                         *(ctypes.byref(m) if m is not None else None for m in structs),
                          _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
-                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS), self._s())
+                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS),
+                         _lib.ptr(bufs.get("records")), self._s())
         self._keep = (net_white, net_black, structs, epsilon, tag, bufs)
         return bufs
 
     def turn_value_rollout_buffers(self, plies, dice=True, play=True, value=True, reward=True, terminated=True,
-                                   truncated=True):
+                                   truncated=True, records=False):
         """Allocate turn_value_rollout()'s [plies][B] buffers:
         value_rollout_buffers() with play (plies,B,4,2) int8 -- the (from,
         die) sub-moves, -1 padded -- in place of actions."""
         t, B, dev = self.torch, self.num_envs, self.device
         plies = int(plies)
         mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
-        return dict(dice=mk(dice, (plies, B, 2), t.uint8), play=mk(play, (plies, B, 4, 2), t.int8),
+        bufs = dict(dice=mk(dice, (plies, B, 2), t.uint8), play=mk(play, (plies, B, 4, 2), t.int8),
                     value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
                     terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
+        if records:  # (the key exists only then: callers walk the dict)
+            bufs["records"] = t.empty((plies, B, 8), dtype=t.int32, device=dev)
+        return bufs
 
     _TURN_VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("play", (4, 2), "int8"), ("value", (), "float32"),
                                 ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
@@ -799,7 +811,8 @@ class VecNardeEnv:
         Returns bufs (turn_value_rollout_buffers(): made when not given; an
         entry None is not written): dice, play (plies,B,4,2) int8, value --
         white's value of the row played, NaN on a random ply and on a pass --,
-        reward, terminated, truncated.
+        reward, terminated, truncated; and, where bufs has it, records
+        (turn_value_rollout_buffers(records=True)).
         scratch: a uint8 device tensor of whole pieces
         (turn_value_rollout_scratch()); the launch has as many one-wave
         workgroups as it has pieces, B at most, and gives the same bits
@@ -822,11 +835,11 @@ class VecNardeEnv:
               or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
             raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
                              f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
-        self.handle.call("narde_turn_value_rollout", plies,
+        self.handle.call("narde_turn_value_rollout_records", plies,
                          *(ctypes.byref(m) if m is not None else None for m in structs),
                          _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
                          *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
-                         _lib.ptr(scratch), int(scratch.numel()), self._s())
+                         _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
         self._keep = (net_white, net_black, structs, epsilon, tag, bufs, scratch)
         return bufs
 

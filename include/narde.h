@@ -491,6 +491,20 @@ int narde_value_rollout(narde_env *env, int plies, const narde_value_mlp *net_wh
                         const int64_t *tag, uint8_t *dice, int16_t *actions, float *value,
                         int32_t *reward, uint8_t *terminated, uint8_t *truncated, void *stream);
 
+/* narde_value_rollout with one more optional output:
+ * records u32[plies][B][8], 16-B aligned -- records[k][e] is env e's 32-byte
+ * record (its two planes, p0 then p1) as ply k found it: after ply k - 1's
+ * step and auto-reset, before ply k's roll is applied.  It is what
+ * narde_value_td_window trains on.  records == NULL is narde_value_rollout
+ * itself, bit for bit; every other output and the final state do not depend
+ * on records.  NARDE_EINVAL: narde_value_rollout's cases, records not 16-B
+ * aligned. */
+int narde_value_rollout_records(narde_env *env, int plies, const narde_value_mlp *net_white,
+                                const narde_value_mlp *net_black, const float *epsilon, uint64_t seed,
+                                const int64_t *tag, uint8_t *dice, int16_t *actions, float *value,
+                                int32_t *reward, uint8_t *terminated, uint8_t *truncated,
+                                void *records, void *stream);
+
 /* narde_afterstates_scored over narde_turn_afterstates' rows (FULL4), the overflow path
  * included; that call's workspace rule holds (the handle's first call of
  * either, outside capture). */
@@ -595,6 +609,16 @@ int narde_turn_value_rollout(narde_env *env, int plies, const narde_value_mlp *n
                              int32_t *reward, uint8_t *terminated, uint8_t *truncated,
                              void *scratch, int64_t scratch_bytes, void *stream);
 
+/* narde_turn_value_rollout with narde_value_rollout_records' optional output
+ * (the same layout and the same moment of a ply).  NARDE_EINVAL:
+ * narde_turn_value_rollout's cases, records not 16-B aligned. */
+int narde_turn_value_rollout_records(narde_env *env, int plies, const narde_value_mlp *net_white,
+                                     const narde_value_mlp *net_black, const float *epsilon,
+                                     uint64_t seed, const int64_t *tag, uint8_t *dice, int8_t *play,
+                                     float *value, int32_t *reward, uint8_t *terminated,
+                                     uint8_t *truncated, void *scratch, int64_t scratch_bytes,
+                                     void *records, void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
  * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
@@ -661,6 +685,49 @@ int narde_value_td_apply(narde_env *env, const narde_value_mlp_train *net, float
                          const uint8_t *terminated, const uint8_t *truncated, float alpha, float gamma,
                          int perspective, float *scratch, int64_t scratch_floats, float *delta,
                          void *stream);
+
+/* Windowed (truncated) TD(lambda): one weight update from a recorded window
+ * of K = plies plies.  records u32[K][B][8], reward
+ * i32[K][B], terminated and truncated u8[K][B] are laid out as the records
+ * rollouts above write them; the call does not care how they were produced.
+ * Under the weights as they are on entry, per env e:
+ *   s_k = records[k][e] for k < K, s_K = the env's record as it stands;
+ *   v_k = v(s_k), white's value, k = 0 .. K; black_k = s_k's mover bit;
+ *   target_k = the outcome -- reward[k], negated when black_k -- if
+ *              terminated[k], v_k if truncated[k], else gamma * v_{k+1};
+ *   delta_k = target_k - v_k, written to delta f32[K][B] if not NULL;
+ *   G_K = 0, G_k = delta_k + c_k * G_{k+1}, c_k = 0 where ply k ended an
+ *         episode (terminated or truncated), gamma * lam elsewhere;
+ * then theta += alpha * sum_e sum_k G_k * grad_theta v(s_k) into w1t, b1, w2,
+ * b2 and the mirror, the same bits to both.  With the weights fixed over the
+ * window this equals the backward view's sum_k delta_k trace_k; states before
+ * the window get nothing from its errors (no credit crosses the left edge).
+ * No trace array exists: a sample's gradient goes from its record's own
+ * columns straight into an accumulator on chip.  The sum has one order and no
+ * float atomics -- the samples in k * B + e order in slabs of
+ * NARDE_TD_WINDOW_SLAB, every element of a slab's partial row taking its
+ * addends in sample order, then the partial rows in slab order --: the same
+ * inputs give the same bits.
+ * scratch: device memory, 16-B aligned, scratch_floats >=
+ * NARDE_TD_WINDOW_SCRATCH_FLOATS(B, plies, hidden).  On return it holds
+ * v f32[K + 1][B] at its start and G f32[K][B] behind it, (K + 1) * B rounded
+ * up to a multiple of 4 floats in; the rest is unspecified.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable once
+ * the device has seen one call (the first announces the gradient kernel's
+ * LDS).  NARDE_EINVAL before any device call: narde_value_td_trace's net
+ * cases, a NULL env, records, reward, terminated, truncated or scratch,
+ * plies < 1, (plies + 1) * B at or above 2^31, lam outside [0, 1], records or
+ * scratch not 16-B aligned, scratch too small. */
+#define NARDE_TD_WINDOW_SLAB 128
+#define NARDE_TD_WINDOW_SCRATCH_FLOATS(B, plies, hidden)                                          \
+  (((((int64_t)(plies) + 1) * (int64_t)(B) + 3) / 4) * 4 +                                        \
+   (((int64_t)(plies) * (int64_t)(B) + 3) / 4) * 4 +                                              \
+   (((int64_t)(plies) * (int64_t)(B) + NARDE_TD_WINDOW_SLAB - 1) / NARDE_TD_WINDOW_SLAB) *        \
+       (200 * (int64_t)(hidden) + 4))
+int narde_value_td_window(narde_env *env, const narde_value_mlp_train *net, int plies,
+                          const void *records, const int32_t *reward, const uint8_t *terminated,
+                          const uint8_t *truncated, float alpha, float lam, float gamma,
+                          float *scratch, int64_t scratch_floats, float *delta, void *stream);
 
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
