@@ -36,6 +36,12 @@
 //   kernels_turn_value_rollout.h  FULL4 value-greedy games in one launch: the
 //                       picking consumer of the level walk inside a ply loop
 //                       (k_turn_value_rollout)
+//   kernels_value_playout.h  Monte-Carlo playouts of given positions under
+//                       value nets, REF2: the rollout's ply from a caller's
+//                       records to the end of the game (k_state_records,
+//                       k_playout_zero, k_value_playout)
+//   kernels_turn_value_playout.h  the same over FULL4 whole turns
+//                       (k_turn_value_playout)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
 // This file keeps the handle, the host-side checks and every C entry point.
@@ -70,6 +76,8 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_turn_afterstates.h"
 #include "kernels_turn_lookahead.h"
 #include "kernels_turn_value_rollout.h"
+#include "kernels_value_playout.h"
+#include "kernels_turn_value_playout.h"
 #include "kernels_td.h"
 #include "kernels_td_window.h"
 
@@ -877,6 +885,108 @@ int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net
                              uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* stream) {
   return narde_turn_value_rollout_records(e, plies, net_white, net_black, epsilon, seed, tag, dice, play, value, reward,
                                           terminated, truncated, scratch, scratch_bytes, nullptr, stream);
+}
+
+int narde_state_records(int device, int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* first_turn,
+                        const int8_t* player, uint32_t t, void* records, void* stream) {
+  if (!board || !off || !first_turn || !player || !records) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 1 || n >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "n %lld outside 1 .. 2^31 - 1", (long long)n);
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  DeviceGuard dg(device);
+  k_state_records<<<grid(n), kBlock, 0, (hipStream_t)stream>>>(n, board, off, first_turn, player, t, (uint4*)records);
+  return check_launch("k_state_records");
+}
+
+namespace {
+
+// The playouts' (narde_value_playout, narde_turn_value_playout) checks, and
+// the kernels' arguments (the slab is the FULL4 call's own)
+int check_playout(const narde_env* e, int64_t n, const void* roots, int trials, int max_plies,
+                  const narde_value_mlp* net_white, const narde_value_mlp* net_black, uint64_t seed, int64_t id_base,
+                  int flags, int32_t* sums, int8_t* outcome, int32_t* length, float* leaf, VpArgs& a, ValNet& vw,
+                  ValNet& vb) {
+  if (!e || !roots || !sums) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 1 || trials < 1 || max_plies < 1)
+    return fail(NARDE_EINVAL, "n %lld, trials %d and max_plies %d must all be at least 1", (long long)n, trials,
+                max_plies);
+  constexpr int64_t k31 = int64_t(1) << 31;
+  if (n >= k31 || n * (int64_t)trials >= k31)
+    return fail(NARDE_EINVAL, "n x trials must stay below 2^31 (n %lld, trials %d)", (long long)n, trials);
+  if ((int64_t)trials * (int64_t)max_plies >= k31)
+    return fail(NARDE_EINVAL, "trials x max_plies must stay below 2^31 (trials %d, max_plies %d)", trials, max_plies);
+  if (flags & ~NARDE_PLAYOUT_COMMON_DICE) return fail(NARDE_EINVAL, "unknown flags 0x%x", (unsigned)flags);
+  if (!aligned16(roots)) return fail(NARDE_EINVAL, "roots must be 16-B aligned");
+  if (id_base < 0 || id_base + n * (int64_t)trials >= (int64_t(1) << 32))
+    return fail(NARDE_EINVAL, "id_base %lld: the trials' env ids must lie in 0 .. 2^32 - 1", (long long)id_base);
+  if (!net_white && !net_black)
+    return fail(NARDE_EINVAL, "no net for either colour: a playout needs a value net");
+  if (net_white)
+    if (const int rc = check_value_mlp(net_white, 1, nullptr, kValLdMax, vw)) return rc;
+  if (net_black)
+    if (const int rc = check_value_mlp(net_black, 1, nullptr, kValLdMax, vb)) return rc;
+  a = VpArgs{(const uint4*)roots,
+             (int)n,
+             trials,
+             max_plies,
+             Rng{(uint32_t)id_base, (uint32_t)seed, (uint32_t)(seed >> 32), e->dice_mode},
+             (flags & NARDE_PLAYOUT_COMMON_DICE) != 0,
+             sums,
+             outcome,
+             length,
+             leaf,
+             nullptr};
+  return NARDE_OK;
+}
+
+// sums = 0 ahead of the trials' atomic adds: a kernel of the library's own, not
+// hipMemsetAsync -- a captured memset node of this size replayed other bytes
+// than zeros under torch.cuda.graph on ROCm 7
+int zero_playout_sums(int32_t* sums, int64_t n, hipStream_t stream) {
+  k_playout_zero<<<grid(4 * n), kBlock, 0, stream>>>(sums, 4 * n);
+  return check_launch("k_playout_zero");
+}
+
+}  // namespace
+
+int narde_value_playout(narde_env* e, int64_t n, const void* roots, int trials, int max_plies,
+                        const narde_value_mlp* net_white, const narde_value_mlp* net_black, uint64_t seed,
+                        int64_t id_base, int flags, int32_t* sums, int8_t* outcome, int32_t* length, float* leaf,
+                        void* stream) {
+  VpArgs a{};
+  ValNet vw{}, vb{};
+  if (const int rc = check_playout(e, n, roots, trials, max_plies, net_white, net_black, seed, id_base, flags, sums,
+                                   outcome, length, leaf, a, vw, vb))
+    return rc;
+  DeviceGuard dg(e->device);
+  if (const int rc = zero_playout_sums(sums, n, (hipStream_t)stream)) return rc;
+  k_value_playout<<<(unsigned)(n * trials), 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                          net_black != nullptr);
+  return check_launch("k_value_playout");
+}
+
+int narde_turn_value_playout(narde_env* e, int64_t n, const void* roots, int trials, int max_plies,
+                             const narde_value_mlp* net_white, const narde_value_mlp* net_black, uint64_t seed,
+                             int64_t id_base, int flags, int32_t* sums, int8_t* outcome, int32_t* length, float* leaf,
+                             void* scratch, int64_t scratch_bytes, void* stream) {
+  VpArgs a{};
+  ValNet vw{}, vb{};
+  if (const int rc = check_playout(e, n, roots, trials, max_plies, net_white, net_black, seed, id_base, flags, sums,
+                                   outcome, length, leaf, a, vw, vb))
+    return rc;
+  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
+  if (pieces < 1)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
+                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  DeviceGuard dg(e->device);
+  const int64_t total = n * trials;
+  const int64_t waves = pieces < total ? pieces : total;
+  a.slab = (uint8_t*)scratch;
+  if (const int rc = zero_playout_sums(sums, n, (hipStream_t)stream)) return rc;
+  k_turn_value_playout<<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
+                                                                        net_black != nullptr);
+  return check_launch("k_turn_value_playout");
 }
 
 int narde_turn_afterstates(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,

@@ -51,6 +51,8 @@ def turn_rollout_scratch_bytes(waves):
     return 83536 * int(waves)
 
 
+PLAYOUT_COMMON_DICE = 1  # NARDE_PLAYOUT_COMMON_DICE
+
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
 
@@ -131,6 +133,11 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "narde_turn_value_rollout_records": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "narde_state_records": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "narde_value_playout": (_i32, [_vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _u64,
+                                   _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "narde_turn_value_playout": (_i32, [_vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp),
+                                        _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

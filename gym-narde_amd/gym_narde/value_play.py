@@ -163,3 +163,15 @@ def _match(env, buffers, column, rollout, net_a, net_b, plies, epsilon, seed):
         by[name] = {"games": games, "points_a": pa, "points_b": pbb}
     return {"games": sum(v["games"] for v in by.values()), "points_a": sum(v["points_a"] for v in by.values()),
             "points_b": sum(v["points_b"] for v in by.values()), "by_colour": by}
+
+
+def playout_values(env, roots, net, trials, max_plies=1000, seed=0, id_base=0, common_dice=False, truncated=False):
+    """What the positions `roots` are worth to white when both colours play
+    value-greedy under `net` to the end: env.playout() with one net, reduced to
+    (mean, stderr), float64 device tensors of one entry a root (DESIGN.md
+    section 22).  roots: (N, 8) int32 records or a get_state()-style dict.
+    truncated: count a trial max_plies cut short at the net's value of the
+    position it stopped at (mean over all trials) instead of leaving it out."""
+    res = env.playout(roots, trials, net, max_plies=max_plies, seed=seed, id_base=id_base, common_dice=common_dice,
+                      leaf=truncated)
+    return res.mean(truncated=truncated), res.stderr()

@@ -134,6 +134,46 @@ _FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAftersta
 _SAME = object()  # value_rollout(): "net_black is net_white"
 
 
+class PlayoutResult:
+    """VecNardeEnv.playout()'s result for N roots of `trials` trials each:
+    sums (N, 4) int32 -- its columns finished (trials that reached the end),
+    points (the sum of white's outcomes, each +-1 or +-2), squares (the sum of
+    their squares) and plies (played by all trials) --, and the optional
+    per-trial outcome (N, trials) int8, length (N, trials) int32 and leaf
+    (N, trials) float32 (white's value where a trial stopped unfinished, NaN
+    where it finished).  Device tensors; reading them synchronises."""
+
+    def __init__(self, sums, trials, outcome=None, length=None, leaf=None):
+        self.sums, self.trials = sums, int(trials)
+        self.outcome, self.length, self.leaf = outcome, length, leaf
+
+    finished = property(lambda self: self.sums[:, 0])
+    points = property(lambda self: self.sums[:, 1])
+    squares = property(lambda self: self.sums[:, 2])
+    plies = property(lambda self: self.sums[:, 3])
+
+    def mean(self, truncated=False):
+        """White's mean outcome per root, float64: over the finished trials
+        (NaN where none finished), or with truncated=True over all trials, an
+        unfinished one counted at its leaf value: (points +
+        nansum(leaf)) / trials, summed in index order."""
+        import torch
+
+        pts = self.points.double()
+        if not truncated:
+            return pts / self.finished.double()
+        if self.leaf is None:
+            raise ValueError("mean(truncated=True) needs playout(leaf=True)")
+        return (pts + torch.nansum(self.leaf.cpu().double(), dim=1).to(pts.device)) / self.trials
+
+    def stderr(self):
+        """The standard error of mean() over the finished trials, float64
+        (NaN with fewer than two)."""
+        f, pts, sq = self.finished.double(), self.points.double(), self.squares.double()
+        var = (sq - pts * pts / f) / (f - 1.0)
+        return (var.clamp(min=0.0) / f).sqrt().masked_fill(f < 2.0, float("nan"))
+
+
 class VecNardeEnv:
     def __init__(self, num_envs, device=None, seed=0, env_id_offset=0, dice_mode="all36",
                  max_episode_steps=1000, autoreset=True, rules="ref2"):
@@ -842,6 +882,93 @@ class VecNardeEnv:
                          _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
         self._keep = (net_white, net_black, structs, epsilon, tag, bufs, scratch)
         return bufs
+
+    def state_records(self, board, off, first_turn, player, t=0):
+        """N positions (set_state()'s arrays, any N) as the 32-byte records
+        the records rollouts write: an (N, 8) int32 device tensor, the ply
+        counter t, elapsed 0 (narde_state_records).  What playout() takes as
+        roots and td.WindowTDLambdaLearner as records."""
+        tt = self.torch
+        b = tt.as_tensor(board, device=self.device).to(tt.int8).contiguous()
+        if b.dim() != 2 or b.shape[1] != 24 or b.shape[0] < 1:
+            raise ValueError(f"board must be (N, 24) with N >= 1, got {tuple(b.shape)}")
+        N = int(b.shape[0])
+        o = self._dev(off, tt.uint8, (N, 2))
+        f = self._dev(first_turn, tt.uint8, (N, 2))
+        p = self._dev(player, tt.int8, (N,))
+        rec = tt.empty((N, 8), dtype=tt.int32, device=self.device)
+        _lib.check(self.handle.lib.narde_state_records(self.device.index, N, _lib.ptr(b), _lib.ptr(o), _lib.ptr(f),
+                                                       _lib.ptr(p), int(t) & 0xFFFFFFFF, _lib.ptr(rec), self._s()),
+                   "narde_state_records")
+        self._keep = (b, o, f, p)
+        return rec
+
+    def playout(self, roots, trials, net_white, net_black=_SAME, max_plies=1000, seed=0, id_base=0,
+                common_dice=False, per_trial=False, leaf=False, scratch=None, out=None):
+        """Monte-Carlo playouts (narde_value_playout / narde_turn_value_playout
+        by the env's rules): every root position played
+        `trials` times to the end -- max_plies plies at most -- both colours
+        value-greedy under their nets (None: that colour plays the
+        random-legal policy), each trial on a dice stream of its own.  roots:
+        an (N, 8) int32 device tensor of records (state_records(), or a
+        records rollout's bufs["records"][k]) or a get_state()-style dict,
+        packed with state_records() at ply counter 0.  Trial j of root i plays
+        what value_rollout() / turn_value_rollout() plays at env index
+        i * trials + j of an env made with `seed`, env_id_offset=id_base, this
+        env's dice mode and max_episode_steps=0, up to its first terminal ply;
+        common_dice: index j for every root, so that all roots see the same
+        dice in trial j.  This env's own positions, ply counter and
+        statistics are neither read nor written.
+        Returns a PlayoutResult: finished, points, squares, plies -- (N,)
+        int32 views of its sums --, and with per_trial outcome (N, trials)
+        int8 and length (N, trials) int32, with leaf the (N, trials) float32
+        leaf values of the unfinished trials (NaN where finished).  out: an
+        earlier result of the same shape to write into (no allocation: graph
+        capture).  scratch (full4): as turn_value_rollout()'s; not given, it is
+        allocated at min(N * trials, resident waves) pieces, kept on the env
+        and grown when a later call needs more -- a caller capturing a graph
+        makes its first call outside capture or passes its own.  The same
+        inputs give the same bits whatever its size.  No synchronise."""
+        t = self.torch
+        if isinstance(roots, dict):
+            roots = self.state_records(roots["board"], roots["off"], roots["first_turn"], roots["player"])
+        if (not isinstance(roots, t.Tensor) or roots.dtype != t.int32 or roots.device != self.device
+                or not roots.is_contiguous() or roots.dim() != 2 or roots.shape[1] != 8 or roots.shape[0] < 1):
+            raise ValueError("roots must be a contiguous (N, 8) int32 device tensor of records, or a get_state() dict")
+        N, trials, max_plies = int(roots.shape[0]), int(trials), int(max_plies)
+        if trials < 1 or max_plies < 1:
+            raise ValueError("trials and max_plies must be >= 1")
+        _, net_white, net_black, structs, _, _, _ = self._value_rollout_args(1, net_white, net_black, None, None, {},
+                                                                             None, ())
+        if out is None:
+            mk = lambda on, dt: t.empty((N, trials), dtype=dt, device=self.device) if on else None  # noqa: E731
+            out = PlayoutResult(t.empty((N, 4), dtype=t.int32, device=self.device), trials, mk(per_trial, t.int8),
+                                mk(per_trial, t.int32), mk(leaf, t.float32))
+        elif tuple(out.sums.shape) != (N, 4) or out.trials != trials or out.sums.device != self.device:
+            raise ValueError("out must be a PlayoutResult of the same roots and trials on this device")
+        args = [N, _lib.ptr(roots), trials, max_plies, *(ctypes.byref(m) if m is not None else None for m in structs),
+                int(seed) & (2 ** 64 - 1), int(id_base), _lib.PLAYOUT_COMMON_DICE if common_dice else 0,
+                _lib.ptr(out.sums), _lib.ptr(out.outcome), _lib.ptr(out.length), _lib.ptr(out.leaf)]
+        if self.full:
+            if scratch is None:
+                # min(N * trials, resident waves) pieces, kept on the env and grown when a call needs more
+                # (the occupancy query is made once: a later call, inside a graph capture too, makes no other
+                # call than the launch)
+                if getattr(self, "_playout_waves", None) is None:
+                    self._playout_waves = self.turn_value_rollout_waves()
+                need = _lib.turn_rollout_scratch_bytes(min(N * trials, self._playout_waves))
+                if getattr(self, "_playout_scratch", None) is None or self._playout_scratch.numel() < need:
+                    self._playout_scratch = t.empty(need, dtype=t.uint8, device=self.device)
+                scratch = self._playout_scratch
+            elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
+                  or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
+                raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
+                                 f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
+            self.handle.call("narde_turn_value_playout", *args, _lib.ptr(scratch), int(scratch.numel()), self._s())
+        else:
+            self.handle.call("narde_value_playout", *args, self._s())
+        self._keep = (roots, net_white, net_black, structs, out, scratch)
+        return out
 
     def rollout_launcher(self, plies, bufs, events=None, totals=None):
         """rollout(plies, bufs) pre-bound: a zero-argument callable that makes

@@ -619,6 +619,63 @@ int narde_turn_value_rollout_records(narde_env *env, int plies, const narde_valu
                                      uint8_t *truncated, void *scratch, int64_t scratch_bytes,
                                      void *records, void *stream);
 
+/* Monte-Carlo playouts: given positions played to the end under value nets
+ * (DESIGN.md section 22).
+ *
+ * narde_state_records packs n positions (narde_set_state's arrays, device
+ * memory) into the 32-B records the records rollouts write: records u32[n][8],
+ * planes p0 then p1, 16-B aligned, the ply counter t, elapsed 0.  Stateless,
+ * no validation on the device.  NARDE_EINVAL: a NULL array, n < 1, n >= 2^31,
+ * records misaligned.
+ *
+ * narde_value_playout (REF2): roots u32[n][8] records (a records rollout's
+ * output as it stands).  Trial j of root i, local index q = i * trials + j,
+ * plays from roots[i] -- with its t -- exactly the plies narde_value_rollout
+ * (epsilon NULL) plays for an env with that record at env index q of a handle
+ * made with seed, env_id_offset = id_base, the calling handle's dice mode and
+ * max_episode_steps = 0: the same ply stream, expansion, tie and NaN rules,
+ * mover's net, random-legal policy for a NULL net (both NULL: NARDE_EINVAL),
+ * and code-0 exception.  The trial stops after the first ply that terminates,
+ * or after max_plies plies; nothing is reset and no TimeLimit is looked at.
+ * NARDE_PLAYOUT_COMMON_DICE: trial j's env index and id are j and id_base + j
+ * for every root (common random numbers).  Of the handle only the device and
+ * the dice mode are read; nothing of it is written.
+ * Outputs: sums i32[n][4] (required; zeroed by the call) = finished trials,
+ * the sum of white's outcomes (the terminating ply's reward, negated when
+ * black made it), the sum of their squares, the plies played by all trials;
+ * optional outcome i8[n][trials] (0: unfinished), length i32[n][trials], leaf
+ * f32[n][trials]: for an unfinished trial white's value of the record it
+ * stopped at, as narde_value_td_trace's v, under that record's mover's net
+ * (the other colour's if it has none); NaN for a finished trial.  The sums are
+ * integer adds: the same bits for any launch geometry.
+ * A root in which a side has 15 checkers off already is not a position of a
+ * game: its numbers are unspecified.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable (two
+ * kernel nodes: the sums' zeros, the trials).  NARDE_EINVAL before any device call: a NULL
+ * handle, roots or sums; narde_value_rollout's cases for either net; both nets
+ * NULL; n, trials or max_plies < 1; n * trials >= 2^31; trials * max_plies >=
+ * 2^31; an unknown flag; roots not 16-B aligned; id_base < 0 or id_base + n *
+ * trials >= 2^32.
+ *
+ * narde_turn_value_playout (FULL4): the same over narde_turn_value_rollout's
+ * whole turns, a pass when there is no row.  scratch as there: pieces of
+ * NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1), trial q played by wave q mod waves;
+ * the same bits whatever scratch_bytes.  NARDE_EINVAL also: a NULL or
+ * misaligned scratch, scratch_bytes below one piece. */
+int narde_state_records(int device, int64_t n, const int8_t *board, const uint8_t *off,
+                        const uint8_t *first_turn, const int8_t *player, uint32_t t,
+                        void *records, void *stream);
+#define NARDE_PLAYOUT_COMMON_DICE 1
+int narde_value_playout(narde_env *env, int64_t n, const void *roots, int trials, int max_plies,
+                        const narde_value_mlp *net_white, const narde_value_mlp *net_black,
+                        uint64_t seed, int64_t id_base, int flags, int32_t *sums, int8_t *outcome,
+                        int32_t *length, float *leaf, void *stream);
+int narde_turn_value_playout(narde_env *env, int64_t n, const void *roots, int trials, int max_plies,
+                             const narde_value_mlp *net_white, const narde_value_mlp *net_black,
+                             uint64_t seed, int64_t id_base, int flags, int32_t *sums,
+                             int8_t *outcome, int32_t *length, float *leaf, void *scratch,
+                             int64_t scratch_bytes, void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
  * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
