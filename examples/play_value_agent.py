@@ -16,9 +16,13 @@ LookaheadPlayer: lookahead_afterstates, --rules full4:
 lookahead_turn_afterstates over whole-turn replies; --plies is already the
 number of plies played).  --one-launch (depth 1; implies --fused): the
 --plies plies are one launch (VecNardeEnv.value_rollout, --rules full4:
-turn_value_rollout), the same games.
+turn_value_rollout), the same games.  --playout TRIALS [--top K] (either rule
+set, implies --fused): playout-greedy play -- each env's K best rows by one-ply
+value are played out TRIALS times to the end under the same net and the best
+mean outcome is played (value_play's PlayoutPlayer: recorded_afterstates ->
+top_rows -> playout -> pick_playout -> step).
 
-  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2] [--one-launch]
+  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2] [--one-launch] [--playout TRIALS [--top K]]
 """
 import argparse
 import os
@@ -39,10 +43,10 @@ def make_net(seed, device):
 
 
 def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False, depth=1,
-         one_launch=False):
+         one_launch=False, playout=0, top=4):
     import torch
 
-    from gym_narde.value_play import LookaheadPlayer, ValuePlayer
+    from gym_narde.value_play import LookaheadPlayer, PlayoutPlayer, ValuePlayer
     from gym_narde.vector import VecNardeEnv
 
     env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
@@ -56,7 +60,9 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         net.load_state_dict(sd)
     if one_launch and depth != 1:
         raise ValueError("--one-launch is --depth 1")
-    if fused or depth == 2 or one_launch:
+    if playout and (depth != 1 or one_launch or epsilon > 0):
+        raise ValueError("--playout is --depth 1 play, ply by ply, without --epsilon")
+    if fused or depth == 2 or one_launch or playout:
         from gym_narde.value_net import ValueMLP
 
         net = ValueMLP.from_sequential(net)
@@ -67,6 +73,19 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         rollout(plies, net, epsilon=eps, tag=None if eps is None else 0, seed=seed)
         ep, white, black = (int(x) for x in env.stats().sum(0).tolist())
         print(f"{envs} envs x {plies} plies in one launch: {ep} games finished, points white {white} / black {black}")
+        env.close()
+        return ep, white, black
+    if playout:
+        player = PlayoutPlayer(env, net, k=top, trials=playout, seed=seed)
+        rows = played = 0
+        for ply in range(plies):
+            out = player.step()
+            rows += out[5].cap
+            played += int(out[4]["playout"].plies.sum())
+        ep, white, black = (int(x) for x in env.stats().sum(0).tolist())
+        print(f"{envs} envs x {plies} plies, the best {top} rows played out {playout} times each: "
+              f"{rows / (envs * plies):.1f} afterstates per roll, {played / (envs * plies):.0f} playout plies per move, "
+              f"{ep} games finished, points white {white} / black {black}")
         env.close()
         return ep, white, black
     rows = 0
@@ -94,6 +113,9 @@ if __name__ == "__main__":
                     help="2: value every afterstate by the opponent's expected best reply (ref2 and full4)")
     ap.add_argument("--one-launch", action="store_true",
                     help="play the plies in one launch (value_rollout, full4: turn_value_rollout; depth 1)")
+    ap.add_argument("--playout", type=int, default=0, metavar="TRIALS",
+                    help="playout-greedy play: TRIALS playouts of each of the best --top rows (ref2 and full4)")
+    ap.add_argument("--top", type=int, default=4, metavar="K", help="the candidates a roll's playouts choose among")
     a = ap.parse_args()
     main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused, depth=a.depth,
-         one_launch=a.one_launch)
+         one_launch=a.one_launch, playout=a.playout, top=a.top)

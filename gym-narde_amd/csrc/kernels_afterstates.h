@@ -122,8 +122,9 @@ struct AftRec {
 // number of rows.  kFill: write them from row a.offsets[e] on, below a.cap.
 // kScore (a fill with a.feat NULL): the rows' values under vn as well
 // (kernels_rows.h "the scored rows"; VS the wave's lists).  kRec (a fill
-// with a.feat NULL): the rows' records to *ar as well.
-template <bool kFill, bool kScore = false, bool kRec = false>
+// with a.feat NULL): the rows' records to *ar as well -- kPub: in the public
+// form (kernels_playout_pick.h), the record the step leaves and nothing else.
+template <bool kFill, bool kScore = false, bool kRec = false, bool kPub = false>
 __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftStage* S, const ValNet* vn = nullptr,
                                        ValStage* VS = nullptr, const AftRec* ar = nullptr) {
   const int lane = threadIdx.x & 63;
@@ -166,10 +167,16 @@ __device__ __forceinline__ int aft_env(const AftArgs& a, int e, AftScan& L, AftS
           if constexpr (kRec) {
             uint4 ra, rb;
             side_to_record(c, ra, rb);
-            rb.w = (uint32_t)rew;
-            ar->rec[2 * R] = ra;
-            ar->rec[2 * R + 1] = rb;
-            if (rew != 0) ar->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+            if constexpr (kPub) {
+              record_close_step(rb);
+              ar->rec[2 * R] = ra;
+              ar->rec[2 * R + 1] = rb;
+            } else {
+              rb.w = (uint32_t)rew;
+              ar->rec[2 * R] = ra;
+              ar->rec[2 * R + 1] = rb;
+              if (rew != 0) ar->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+            }
           }
         }
       }

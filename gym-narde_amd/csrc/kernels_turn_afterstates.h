@@ -142,7 +142,9 @@ __device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const Tu
 // with a.feat NULL): the rows' records to *tr as well.  kLook (no fill): the
 // rows' values under vn against lk->vr reduced to the replier's best, left in
 // lk->best.  kPick (with kLook; lk is a TurnPick): the best row and its path
-// kept in place of the reduction.
+// kept in place of the reduction.  kPub (with kRec): tr->row is the public
+// dense output, 8 words a row (kernels_playout_pick.h): the record the step
+// leaves and nothing else.
 // (The walk and its consumers are one function on purpose, and the existing
 // instantiations compile to the instructions they had: with the walk a
 // function of its own that hands the final level to its callers -- by
@@ -150,7 +152,8 @@ __device__ __forceinline__ Side turn_position(const TurnArgs& a, int e, const Tu
 // wrapper -- k_turn_overflow_scored ran 2 to 7 % and k_turn_fill_scored up to
 // 2 % slower than before, outside the runs' spread; DESIGN.md section 18.2,
 // MEASUREMENT_LOG M.34.)
-template <bool kFill, bool kScore = false, bool kRec = false, bool kLook = false, bool kPick = false>
+template <bool kFill, bool kScore = false, bool kRec = false, bool kLook = false, bool kPick = false,
+          bool kPub = false>
 __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt, uint32_t* pathA, uint32_t* pathB,
                                         int room, TurnScan& L, AftStage* S, const ValNet* vn = nullptr,
                                         ValStage* VS = nullptr, const TurnRec* tr = nullptr, TurnLook* lk = nullptr) {
@@ -281,12 +284,19 @@ __device__ __forceinline__ int turn_env(const TurnArgs& a, int e, uint64_t* knxt
         if constexpr (kRec) {
           uint4 ra, rb;
           side_to_record(c, ra, rb);
-          rb.w = (uint32_t)rew;
-          uint4* const row = reinterpret_cast<uint4*>(tr->row + R * kTurnLookRowWords);
-          row[0] = ra;
-          row[1] = rb;
-          tr->row[R * kTurnLookRowWords + kTurnLookRedo] = 0u;
-          if (rew != 0) tr->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+          if constexpr (kPub) {
+            record_close_step(rb);
+            uint4* const row = reinterpret_cast<uint4*>(tr->row + R * 8);
+            row[0] = ra;
+            row[1] = rb;
+          } else {
+            rb.w = (uint32_t)rew;
+            uint4* const row = reinterpret_cast<uint4*>(tr->row + R * kTurnLookRowWords);
+            row[0] = ra;
+            row[1] = rb;
+            tr->row[R * kTurnLookRowWords + kTurnLookRedo] = 0u;
+            if (rew != 0) tr->value[R] = val_outcome(rew, (rb.z >> 10) & 1u, 1);
+          }
         }
       }
       if (a.feat) aft_flush_feat(a.feat, a.cap, row0 + g0, min(64, nrows - g0), *S, lane);

@@ -42,6 +42,11 @@
 //                       k_playout_zero, k_value_playout)
 //   kernels_turn_value_playout.h  the same over FULL4 whole turns
 //                       (k_turn_value_playout)
+//   kernels_playout_pick.h  playout-greedy play: the scored fills with the
+//                       rows' records as an output, an env's top-K rows as
+//                       playout roots, the pick over the playouts' sums
+//                       (k_aft_fill_records, k_turn_fill_records,
+//                       k_rows_topk, k_playout_pick)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
 // This file keeps the handle, the host-side checks and every C entry point.
@@ -78,6 +83,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_turn_value_rollout.h"
 #include "kernels_value_playout.h"
 #include "kernels_turn_value_playout.h"
+#include "kernels_playout_pick.h"
 #include "kernels_td.h"
 #include "kernels_td_window.h"
 
@@ -235,14 +241,22 @@ int check_td(const narde_env* e, const narde_value_mlp_train* net, const float* 
 }
 
 // REF2's expansion: the count pass, the scan, and the fill -- with the
-// rows' values (vn) the scored one
-int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t st) {
+// rows' values (vn) the scored one, with the rows' public records (pub) the
+// records fills of narde_afterstates_records
+int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t st, const AftRec* pub = nullptr) {
   const int cw = kAftCountBlock / 64, fw = kAftFillBlock / 64;
   k_aft_count<<<(unsigned)((e->n + cw - 1) / cw), kAftCountBlock, 0, st>>>(a);
   if (const int rc = check_launch("k_aft_count")) return rc;
   k_aft_scan<<<1, kAftScanBlock, 0, st>>>(a.offsets, (int)e->n);
   if (const int rc = check_launch("k_aft_scan")) return rc;
-  if (a.cap == 0 || !(a.row_env || a.codes || a.feat || a.obs || a.reward || vn)) return NARDE_OK;
+  if (a.cap == 0 || !(a.row_env || a.codes || a.feat || a.obs || a.reward || vn || pub)) return NARDE_OK;
+  if (pub) {
+    if (vn)
+      k_aft_fill_scored_records<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a, *vn, *pub);
+    else
+      k_aft_fill_records<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a, *pub);
+    return check_launch("k_aft_fill_records");
+  }
   if (vn) {
     k_aft_fill_scored<<<(unsigned)((e->n + fw - 1) / fw), kAftFillBlock, 0, st>>>(a, *vn);
     return check_launch("k_aft_fill_scored");
@@ -253,10 +267,11 @@ int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t s
 
 // FULL4's: the handle's workspace on its first call, the count passes, the
 // scan, the fills (scored with vn; with tr the record fills of the lookahead,
-// whose own passes the caller launches behind them)
+// whose own passes the caller launches behind them; with pub the records fills
+// of narde_turn_afterstates_records, scored if vn is given)
 int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env, int8_t* play,
                  float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st,
-                 const TurnRec* tr = nullptr) {
+                 const TurnRec* tr = nullptr, const TurnRec* pub = nullptr) {
   if (!e->turn_slab) {
     // the workspace belongs to the handle and is made once, outside capture
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -283,7 +298,20 @@ int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offset
   if (const int rc = check_launch("k_turn_overflow<count>")) return rc;
   k_aft_scan<<<1, kAftScanBlock, 0, st>>>(offsets, (int)e->n);
   if (const int rc = check_launch("k_aft_scan")) return rc;
-  if (cap == 0 || !(row_env || play || feat || obs || reward || vn || tr)) return NARDE_OK;
+  if (cap == 0 || !(row_env || play || feat || obs || reward || vn || tr || pub)) return NARDE_OK;
+  if (pub) {
+    const unsigned g = (unsigned)((e->n + fw - 1) / fw);
+    if (vn) {
+      k_turn_fill_records<true><<<g, kTurnFillBlock, 0, st>>>(a, *vn, *pub);
+      if (const int rc = check_launch("k_turn_fill_records")) return rc;
+      k_turn_overflow_records<true><<<kTurnOvfWaves, 64, 0, st>>>(a, *vn, *pub);
+    } else {
+      k_turn_fill_records<false><<<g, kTurnFillBlock, 0, st>>>(a, ValNet{}, *pub);
+      if (const int rc = check_launch("k_turn_fill_records")) return rc;
+      k_turn_overflow_records<false><<<kTurnOvfWaves, 64, 0, st>>>(a, ValNet{}, *pub);
+    }
+    return check_launch("k_turn_overflow_records");
+  }
   if (tr) {
     k_turn_fill_rec<<<(unsigned)((e->n + fw - 1) / fw), kTurnFillBlock, 0, st>>>(a, *tr);
     if (const int rc = check_launch("k_turn_fill_rec")) return rc;
@@ -322,6 +350,39 @@ int pick_rows(narde_env* e, const int32_t* offsets, const void* column, int64_t 
       e->pl, (int)e->n, offsets, static_cast<const W*>(column), cap, value, ld_value, perspective, epsilon, tag,
       (uint32_t)seed, (uint32_t)(seed >> 32), static_cast<W*>(out), row);
   return check_launch(kernel);
+}
+
+// narde_afterstates_records' and narde_turn_afterstates_records' checks behind
+// check_expand's: the records, and the net with its values or neither
+int check_records(const void* records, const narde_value_mlp* net, int perspective, float* value, ValNet& vn) {
+  if (!records) return fail(NARDE_EINVAL, "NULL records (without them the call is the scored expansion)");
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  if ((net != nullptr) != (value != nullptr))
+    return fail(NARDE_EINVAL, "net and value must both be set or both be NULL");
+  if (net) return check_value_net(net, perspective, value, vn);
+  return NARDE_OK;
+}
+
+// narde_playout_pick's and narde_turn_playout_pick's checks and launch, as
+// pick_rows: words W of the kind's action column, kNoRow for no candidate
+template <typename W, int kNoRow>
+int playout_pick_rows(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value, int64_t ld_value,
+                      const int8_t* reward, const void* column, int trials, const int32_t* sums, const float* leaf,
+                      void* out, int32_t* row, float* score, void* stream, const char* misaligned) {
+  if (!e || !sel || !value || !reward || !sums || !column || !out) return fail(NARDE_EINVAL, "NULL argument");
+  if (k < 1 || k > NARDE_TOPK_MAX) return fail(NARDE_EINVAL, "k %d outside 1 .. NARDE_TOPK_MAX = %d", k, NARDE_TOPK_MAX);
+  if (trials < 1) return fail(NARDE_EINVAL, "trials %d must be at least 1", trials);
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if (e->n * (int64_t)k * (int64_t)trials >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "B x k x trials must stay below 2^31 (k %d, trials %d)", k, trials);
+  if ((reinterpret_cast<uintptr_t>(column) % sizeof(W)) || (reinterpret_cast<uintptr_t>(out) % sizeof(W)))
+    return fail(NARDE_EINVAL, "%s", misaligned);
+  DeviceGuard dg(e->device);
+  const PlayoutPickArgs a{e->pl, (int)e->n, k, trials, sel, cap, value, ld_value, reward, sums, leaf, row, score};
+  k_playout_pick<W, kNoRow><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(a, static_cast<const W*>(column),
+                                                                            static_cast<W*>(out));
+  return check_launch("k_playout_pick");
 }
 
 }  // namespace
@@ -1046,6 +1107,72 @@ int narde_turn_afterstates_lookahead(narde_env* e, const uint8_t* dice, int64_t 
   k_turn_look_mean<<<(unsigned)((rows + kTurnLookMeanBlock - 1) / kTurnLookMeanBlock), kTurnLookMeanBlock, 0, st>>>(
       la, value);
   return check_launch("k_turn_look_mean");
+}
+
+int narde_afterstates_records(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
+                              int16_t* codes, int8_t* reward, const narde_value_mlp* net, int perspective,
+                              float* value, void* records, void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, kAftMaxPlays, nullptr, nullptr, codes, 4,
+                                  "codes must be 4-B aligned"))
+    return rc;
+  ValNet vn{};
+  if (const int rc = check_records(records, net, perspective, value, vn)) return rc;
+  DeviceGuard dg(e->device);
+  const AftRec pub{(uint4*)records, nullptr};
+  return expand_plays(e, AftArgs{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, codes, nullptr, nullptr,
+                                 reward},
+                      net ? &vn : nullptr, (hipStream_t)stream, &pub);
+}
+
+int narde_turn_afterstates_records(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets,
+                                   int32_t* row_env, int8_t* play, int8_t* reward, const narde_value_mlp* net,
+                                   int perspective, float* value, void* records, void* stream) {
+  if (const int rc = check_expand(e, cap, offsets, NARDE_TURN_AFT_MAX, nullptr, nullptr, play, 8,
+                                  "play must be 8-B aligned"))
+    return rc;
+  ValNet vn{};
+  if (const int rc = check_records(records, net, perspective, value, vn)) return rc;
+  DeviceGuard dg(e->device);
+  const TurnRec pub{(uint32_t*)records, nullptr};
+  return expand_turns(e, dice, cap, offsets, row_env, play, nullptr, nullptr, reward, net ? &vn : nullptr,
+                      (hipStream_t)stream, nullptr, &pub);
+}
+
+static_assert(kRecordNoneWord6 == NARDE_RECORD_NONE_WORD6, "narde.h and narde_rules.h state the same none record");
+
+int narde_rows_topk(narde_env* e, const int32_t* offsets, int64_t cap, const float* value, int64_t ld_value,
+                    int perspective, int k, const void* records, int32_t* sel, void* roots, void* stream) {
+  if (!e || !offsets || !value || !sel) return fail(NARDE_EINVAL, "NULL argument");
+  if (k < 1 || k > NARDE_TOPK_MAX) return fail(NARDE_EINVAL, "k %d outside 1 .. NARDE_TOPK_MAX = %d", k, NARDE_TOPK_MAX);
+  if (perspective != 0 && perspective != 1)
+    return fail(NARDE_EINVAL, "perspective must be 0 (the mover's values) or 1 (white's)");
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if ((roots != nullptr) != (records != nullptr))
+    return fail(NARDE_EINVAL, "roots and records must both be set or both be NULL");
+  if (!aligned16(roots) || !aligned16(records)) return fail(NARDE_EINVAL, "roots and records must be 16-B aligned");
+  if (e->n * (int64_t)k >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "B x k must stay below 2^31 (k %d)", k);
+  DeviceGuard dg(e->device);
+  const TopkArgs a{e->pl, (int)e->n, offsets, cap, value, ld_value, perspective, k, (const uint4*)records, sel,
+                   (uint4*)roots};
+  const int w = kTopkBlock / 64;
+  k_rows_topk<<<(unsigned)((e->n + w - 1) / w), kTopkBlock, 0, (hipStream_t)stream>>>(a);
+  return check_launch("k_rows_topk");
+}
+
+int narde_playout_pick(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value, int64_t ld_value,
+                       const int8_t* reward, const int16_t* codes, int trials, const int32_t* sums, const float* leaf,
+                       int16_t* actions, int32_t* row, float* score, void* stream) {
+  return playout_pick_rows<uint32_t, 0>(e, k, sel, cap, value, ld_value, reward, codes, trials, sums, leaf, actions,
+                                        row, score, stream, "codes and actions must be 4-B aligned");
+}
+
+int narde_turn_playout_pick(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value,
+                            int64_t ld_value, const int8_t* reward, const int8_t* play, int trials,
+                            const int32_t* sums, const float* leaf, int8_t* out_play, int32_t* row, float* score,
+                            void* stream) {
+  return playout_pick_rows<uint64_t, -1>(e, k, sel, cap, value, ld_value, reward, play, trials, sums, leaf, out_play,
+                                         row, score, stream, "play and out_play must be 8-B aligned");
 }
 
 int narde_value_td_trace(narde_env* e, const narde_value_mlp_train* net, float decay, float* trace, int64_t ld_trace,

@@ -2766,4 +2766,59 @@ NARDE_FN void row_best_offer(RowBest& b, float v, int ord, uint32_t codes, bool 
 }
 NARDE_FN uint32_t pack_codes(int c1, int c2) { return (uint32_t)(uint16_t)c1 | ((uint32_t)(uint16_t)c2 << 16); }
 
+// ------------------------------------------------- playout-greedy play
+// An afterstate's record (play_afterstate / a carried-out turn, side_to_record)
+// -> the record the step that plays it leaves in the env: ply_close's
+// elapsed + 1 and t + 1, auto-reset off and no TimeLimit looked at.
+NARDE_FN void record_close_step(uint4& b) {
+  b.z += 1u << 16;
+  b.w += 1u;
+}
+
+// "no root": an empty board with both sides' 15 checkers off
+constexpr uint32_t kRecordNoneWord6 = 0xFFu;
+
+// Round i of the top-K selection offers row q's x only if the round before's
+// choice (px, pi) is strictly ahead of it in argmax_takes' total order: the
+// rows come out best first and none twice, with no list of the chosen.
+NARDE_FN bool topk_offers(float px, int pi, float x, int q) { return pi < 0 || argmax_takes(px, pi, x, q); }
+
+// A candidate's score over its playouts (white's points a game): a terminal
+// row's known outcome v; without leaves the mean outcome of the finished
+// trials, the one-ply value v when none finished; with leaves the truncated
+// mean -- the points plus the unfinished trials' leaves (added in trial order,
+// in double) over all trials.  sums = {finished, points, squares, plies}.
+NARDE_FN float playout_slot_score(int rew, float v, const int32_t* sums, const float* leaf, int trials) {
+  if (rew != 0) return v;
+  if (!leaf) return sums[0] > 0 ? (float)((double)sums[1] / (double)sums[0]) : v;
+  double S = 0.0;
+  for (int j = 0; j < trials; ++j) {
+    const float lf = leaf[j];
+    if (!__builtin_isnan(lf)) S += (double)lf;
+  }
+  return (float)(((double)sums[1] + S) / (double)trials);
+}
+
+// The slot to play among k candidates (sel[s] < 0: none) by score: the largest
+// when white moves, the smallest when black does, the lowest slot on ties,
+// NaN as argmax_takes takes it.  score (optional): every slot's, NaN for none.
+NARDE_FN int playout_pick_slot(const int32_t* sel, int k, int64_t cap, const float* value, int64_t ld,
+                               const int8_t* reward, const int32_t* sums, const float* leaf, int trials,
+                               bool smallest, float* score) {
+  float best = 0.0f;
+  int bi = -1;
+  for (int s = 0; s < k; ++s) {
+    const int64_t r = sel[s];
+    float sc = __builtin_nanf("");
+    if (r >= 0 && r < cap) {
+      sc = playout_slot_score(reward[r], value[r * ld], sums + 4 * (int64_t)s,
+                              leaf ? leaf + (int64_t)s * trials : nullptr, trials);
+      const float x = smallest ? -sc : sc;
+      if (argmax_takes(x, s, best, bi)) { best = x; bi = s; }
+    }
+    if (score) score[s] = sc;
+  }
+  return bi;
+}
+
 }  // namespace narde

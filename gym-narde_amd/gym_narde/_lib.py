@@ -52,6 +52,8 @@ def turn_rollout_scratch_bytes(waves):
 
 
 PLAYOUT_COMMON_DICE = 1  # NARDE_PLAYOUT_COMMON_DICE
+TOPK_MAX = 64  # NARDE_TOPK_MAX
+RECORD_NONE_WORD6 = 0xFF  # NARDE_RECORD_NONE_WORD6
 
 DICE_ALL36 = 0
 DICE_NODOUBLES = 1
@@ -138,6 +140,13 @@ SIGNATURES = {
                                    _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_value_playout": (_i32, [_vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp),
                                         _u64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "narde_afterstates_records": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp, _vp,
+                                         _vp]),
+    "narde_turn_afterstates_records": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(ValueMlp), _i32, _vp,
+                                              _vp, _vp]),
+    "narde_rows_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "narde_playout_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_turn_playout_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

@@ -119,6 +119,62 @@ class LookaheadPlayer(ValuePlayer):
         self._lookahead = env.lookahead_turn_afterstates if env.full else env.lookahead_afterstates
 
 
+class PlayoutPlayer:
+    """Playout-greedy play for either rule set: every
+    ply, each env's k best rows by one-ply value under net (a
+    value_net.ValueMLP) are played out `trials` times to the end --
+    max_plies plies at most -- under playout_net (default: net, for both
+    colours), and the candidate with the best mean outcome is played.  Five
+    device calls a ply: recorded_afterstates() / recorded_turn_afterstates(),
+    top_rows(), playout(), pick_playout(), step().
+    common_dice: trial j of every root meets the same dice -- across the envs
+    as well as across one env's candidates (one id per trial for the whole
+    call), which is what makes an env's candidates comparable; False gives
+    every trial of every root a stream of its own.  truncated: an unfinished
+    trial counts at playout_net's value of the position it stopped at (the mean
+    over all trials) instead of being left out.  The playouts' seed of a ply
+    is `seed` plus the env's ply counter, so plies differ; the counter is read
+    when the player is made and advanced by step() (plies stepped by others
+    in between: sync_ply()).  cap: the rows every ply's arrays hold; with it
+    a ply makes no synchronise, and rows past cap are not played.  k = 1
+    plays exactly ValuePlayer's moves."""
+
+    def __init__(self, env, net, k=4, trials=64, max_plies=400, playout_net=None, common_dice=True, truncated=False,
+                 cap=None, seed=0):
+        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+            raise TypeError("PlayoutPlayer needs a gym_narde.value_net.ValueMLP")
+        self.env, self.net = env, net
+        self.playout_net = net if playout_net is None else playout_net
+        self.k, self.trials, self.max_plies = int(k), int(trials), int(max_plies)
+        self.common_dice, self.truncated = bool(common_dice), bool(truncated)
+        self.cap = None if cap is None else int(cap)
+        self.seed = int(seed)
+        self._recorded = env.recorded_turn_afterstates if env.full else env.recorded_afterstates
+        self.sync_ply()
+
+    def sync_ply(self):
+        """Read the env's ply counter again (one synchronise)."""
+        self._ply = self.env.ply
+
+    def step(self):
+        """One ply for every env.  Returns what ValuePlayer.step() returns --
+        (obs, reward, terminated, truncated, info, aft, values, actions) --
+        with sel, score and the PlayoutResult (playout) in info besides dice
+        and row."""
+        env = self.env
+        dice = env.dice()
+        aft, values, records = self._recorded(self.net, dice, cap=self.cap)
+        sel, roots = env.top_rows(aft, values, self.k, records)
+        res = env.playout(roots, self.trials, self.playout_net, max_plies=self.max_plies,
+                          seed=(self.seed + self._ply) & (2 ** 64 - 1), common_dice=self.common_dice,
+                          leaf=self.truncated)
+        actions, row, score = env.pick_playout(aft, values, sel, res, leaf=self.truncated)
+        obs, reward, terminated, truncated, info = env.step(actions)
+        self._ply = (self._ply + 1) & 0xFFFFFFFF
+        info = dict(info, dice=dice, row=row, sel=sel, score=score, playout=res)
+        return obs, reward, terminated, truncated, info, aft, values, actions
+
+
 def play_match(env, net_a, net_b, plies, epsilon=None, seed=0):
     """net_a against net_b (value_net.ValueMLPs on the env's device; net_b
     None: the random-legal policy, the baseline) on a rules="ref2" env, every

@@ -554,6 +554,176 @@ class VecNardeEnv:
             raise ValueError('lookahead_turn_afterstates() is rules="full4" only')
         return self._scored_rows(_FULL4_ROWS, net, dice, cap, "white", out, lookahead=True)
 
+    def _recorded_rows(self, k, net, dice, cap, out):
+        """recorded_afterstates() / recorded_turn_afterstates(): the rows of
+        kind k with their records, and their values when net is given."""
+        B, t = self.num_envs, self.torch
+        mlp = None
+        if net is not None:
+            if not hasattr(net, "struct"):
+                raise TypeError("net must be a gym_narde.value_net.ValueMLP or None")
+            mlp = net.struct()
+            if net.l1.weight.device != self.device:
+                raise ValueError("the net must live on the env's device")
+        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        if out is not None:
+            aft, values, records = out
+            cap = aft.cap if cap is None else int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            for name, a, shape, dt in (("offsets", aft.offsets, (B + 1,), t.int32), ("row_env", aft.row_env, (), t.int32),
+                                       (k.field, getattr(aft, k.field), k.shape, getattr(t, k.dtype)),
+                                       ("reward", aft.reward, (), t.int8), ("values", values, (), t.float32),
+                                       ("records", records, (8,), t.int32)):
+                if a is None and (name in ("row_env", k.field, "reward") or (name == "values" and net is None)):
+                    continue
+                ok = a is not None and a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
+                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
+                if not ok:
+                    raise ValueError(f"out {name} must be a contiguous {dt} device tensor of at least cap rows")
+            aft = aft._replace(feat=None, obs=None)
+        else:
+            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
+            if cap is None:
+                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+                cap = int(offsets[B].item())  # the one synchronise
+            cap = int(cap)
+            if cap < 0:
+                raise ValueError("cap must be >= 0")
+            mk = lambda shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device)  # noqa: E731
+            aft = k.tuple(offsets, mk((), t.int32), mk(k.shape, getattr(t, k.dtype)), None, None, mk((), t.int8), cap)
+            values = mk((), t.float32) if net is not None else None
+            records = mk((8,), t.int32)
+        if cap == 0:  # the counts alone (no array to write)
+            self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(aft.offsets), None, None, None, None, None, self._s())
+        else:
+            self.handle.call(k.expand + "_records", _lib.ptr(d), cap, _lib.ptr(aft.offsets), _lib.ptr(aft.row_env),
+                             _lib.ptr(getattr(aft, k.field)), _lib.ptr(aft.reward),
+                             ctypes.byref(mlp) if mlp is not None else None, PERSPECTIVES["white"],
+                             _lib.ptr(values) if net is not None else None, _lib.ptr(records), self._s())
+        self._keep = (d, net, mlp)
+        return aft._replace(cap=cap), (values[:cap] if net is not None else None), records[:cap]
+
+    def recorded_afterstates(self, net, dice=None, cap=None, out=None):
+        """scored_afterstates() (perspective "white") with each row's record
+        as a third output (narde_afterstates_records):
+        returns (aft, values, records), records (cap, 8) int32 = the 32-byte
+        record step(aft.codes[r], autoreset off) leaves in env aft.row_env[r],
+        its ply counter included -- a playout() root as it stands.  net None:
+        the records alone, values None.  cap / out as scored_afterstates():
+        cap None makes the one synchronise; cap given, or out = (an
+        Afterstates, a (>= cap,) float32 values tensor or None, a (>= cap, 8)
+        int32 records tensor), none (graph-safe)."""
+        if self.full:
+            raise ValueError('recorded_afterstates() is rules="ref2" only')
+        return self._recorded_rows(_REF2_ROWS, net, dice, cap, out)
+
+    def recorded_turn_afterstates(self, net, dice=None, cap=None, out=None):
+        """rules="full4": recorded_afterstates() over turn_afterstates()' rows
+        (narde_turn_afterstates_records, the overflow path included)."""
+        if not self.full:
+            raise ValueError('recorded_turn_afterstates() is rules="full4" only')
+        return self._recorded_rows(_FULL4_ROWS, net, dice, cap, out)
+
+    def _row_values(self, aft, values):
+        t = self.torch
+        v = values
+        if v.dim() == 2 and v.shape[1] == 1:
+            v = v[:, 0]
+        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
+                or (v.shape[0] > 1 and v.stride(0) < 1)):
+            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
+        return v
+
+    def top_rows(self, aft, values, k, records=None, perspective="white", out=None):
+        """Each env's k best rows of `aft` by `values`, best first
+        (narde_rows_topk), under exactly
+        pick_afterstate()'s / pick_turn()'s greedy order -- perspective, ties to
+        the lowest row, NaNs first --, so sel[:, 0] is the row those return.
+        Returns (sel (B, k) int32, -1 behind an env's last row; roots (B * k, 8)
+        int32 = records[sel] -- the none record, an empty board with both
+        sides' 15 checkers off, in an empty slot -- or None without records).
+        out: (sel, roots or None) of an earlier call to write into.  Call it
+        before the step (it reads who moves).  No synchronise."""
+        if perspective not in PERSPECTIVES:
+            raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
+        B, t, k = self.num_envs, self.torch, int(k)
+        if not 1 <= k <= _lib.TOPK_MAX:
+            raise ValueError(f"k must be in 1 .. {_lib.TOPK_MAX}")
+        v = self._row_values(aft, values)
+        if records is not None and (records.dtype != t.int32 or records.device != self.device
+                                    or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8
+                                    or records.shape[0] < aft.cap):
+            raise ValueError("records must be a contiguous (>= cap, 8) int32 device tensor")
+        if out is not None:
+            sel, roots = out
+        else:
+            sel = t.empty((B, k), dtype=t.int32, device=self.device)
+            roots = t.empty((B * k, 8), dtype=t.int32, device=self.device) if records is not None else None
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            sel.fill_(-1)
+            if roots is not None:
+                roots.zero_()
+                roots[:, 6] = _lib.RECORD_NONE_WORD6
+            return sel, roots
+        self.handle.call("narde_rows_topk", _lib.ptr(aft.offsets), aft.cap, _lib.ptr(v), max(1, v.stride(0)),
+                         PERSPECTIVES[perspective], k, _lib.ptr(records), _lib.ptr(sel), _lib.ptr(roots), self._s())
+        self._keep = (v, records)
+        return sel, roots
+
+    def pick_playout(self, aft, values, sel, result, leaf=False, out=None):
+        """The playout-greedy move (narde_playout_pick / narde_turn_playout_pick
+        by the env's rules): per env the candidate of
+        sel (top_rows()') with the best playout score.  values: white's
+        one-ply values of aft's rows (a perspective "white" call); result: the
+        PlayoutResult of playout() over top_rows()' roots, or a (sums, trials[,
+        leaf]) tuple.  A slot's score: a terminal row's outcome; else the mean
+        outcome of its finished trials (the one-ply value when none
+        finished), or with leaf=True the truncated mean (points + the
+        unfinished trials' leaves) / trials.  The largest when white moves,
+        the smallest when black does, the lowest slot on ties.  Returns
+        (actions (B,2) int16 or play (B,4,2) int8 for step(), row (B,) int32,
+        score (B, k) float32 -- NaN where a slot is empty); -1 and (0, 0) / an
+        all -1 play for an env with no candidate.  out: an earlier call's
+        triple to write into.  Call it before the step.  No synchronise."""
+        t, B = self.torch, self.num_envs
+        kind = _FULL4_ROWS if self.full else _REF2_ROWS
+        if isinstance(result, PlayoutResult):
+            sums, trials, lf = result.sums, result.trials, result.leaf
+        else:
+            sums, trials = result[0], int(result[1])
+            lf = result[2] if len(result) > 2 else None
+        if leaf and lf is None:
+            raise ValueError("leaf=True needs the playouts' leaf values (playout(leaf=True))")
+        lf = lf if leaf else None
+        if sel.dim() != 2 or sel.shape[0] != B or sel.dtype != t.int32 or not sel.is_contiguous():
+            raise ValueError("sel must be top_rows()' (B, k) int32 tensor")
+        k = int(sel.shape[1])
+        if (tuple(sums.shape) != (B * k, 4) or sums.dtype != t.int32 or not sums.is_contiguous()
+                or sums.device != self.device):
+            raise ValueError("result must hold the sums of B * k roots")
+        if lf is not None and (tuple(lf.shape) != (B * k, trials) or lf.dtype != t.float32 or not lf.is_contiguous()):
+            raise ValueError("leaf must be (B * k, trials) float32")
+        v = self._row_values(aft, values)
+        if out is not None:
+            actions, row, score = out
+        else:
+            actions = t.empty((B,) + kind.shape, dtype=getattr(t, kind.dtype), device=self.device)
+            row = t.empty(B, dtype=t.int32, device=self.device)
+            score = t.empty((B, k), dtype=t.float32, device=self.device)
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            actions.fill_(kind.no_row)
+            row.fill_(-1)
+            score.fill_(float("nan"))
+            return actions, row, score
+        self.handle.call("narde_turn_playout_pick" if self.full else "narde_playout_pick", k, _lib.ptr(sel), aft.cap,
+                         _lib.ptr(v), max(1, v.stride(0)), _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)),
+                         trials, _lib.ptr(sums), _lib.ptr(lf), _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score),
+                         self._s())
+        self._keep = (v, sel, sums, lf)
+        return actions, row, score
+
     def _pick_rows(self, k, aft, values, perspective, epsilon, tag, seed):
         """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""
         if perspective not in PERSPECTIVES:

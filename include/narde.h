@@ -676,6 +676,81 @@ int narde_turn_value_playout(narde_env *env, int64_t n, const void *roots, int t
                              int8_t *outcome, int32_t *length, float *leaf, void *scratch,
                              int64_t scratch_bytes, void *stream);
 
+/* Playout-greedy play: a roll's rows with their records, each env's K best
+ * rows as playout roots, and the pick over the playouts' sums (DESIGN.md
+ * section 23).  The chain -- records, top-K, narde_value_playout, pick,
+ * narde_step -- has static shapes and is graph-capturable.
+ *
+ * narde_afterstates_records / narde_turn_afterstates_records:
+ * narde_afterstates_scored / narde_turn_afterstates_scored with one more
+ * output; the rows, their order, offsets, the cap rule, dice == NULL and the
+ * FULL4 workspace rule (the handle's first call outside capture; the overflow
+ * tiers included) are the same, and one expansion is paid.  records
+ * u32[cap][8], 16-B aligned: records[r] is the record narde_step(codes[r],
+ * dice, autoreset = 0) -- FULL4: narde_step_full(play[r], dice, autoreset = 0)
+ * -- leaves in env row_env[r], in the layout the records rollouts write (p0
+ * then p1): the mover flipped unless the row is terminal, the first-turn flags
+ * and elapsed as that step leaves them, word 7 the env's ply counter as the
+ * step leaves it.  Nothing at or past cap is touched.  net == NULL with value
+ * == NULL: the records alone.  NARDE_EINVAL before any device call: the scored
+ * call's cases; records NULL (that is the scored call) or not 16-B aligned;
+ * net and value not both set or both NULL.
+ *
+ * narde_rows_topk (both rule sets: it works on offsets): sel i32[B][k], slots
+ * 0 .. m - 1 with m = min(k, env e's rows below cap) = the env's best rows,
+ * best first, under exactly the picks' order (epsilon NULL): perspective 0 the
+ * largest value[r * ld_value], perspective 1 the largest when white moves (the
+ * env's record) and the smallest when black does, the lowest row on ties, NaNs
+ * first in row order; slots m .. k - 1 are -1.  sel[e][0] is the row
+ * narde_afterstate_pick / narde_turn_pick return.  With records (the call
+ * above's) roots u32[B][k][8] gets roots[e][i] = records[sel[e][i]], an empty
+ * slot the none record: seven zero words and word 6 = NARDE_RECORD_NONE_WORD6
+ * (an empty board, both sides' 15 checkers off).  A wave an env, no atomics,
+ * the same bits on every call.  NARDE_EINVAL: a NULL handle, offsets, value or
+ * sel; k outside 1 .. NARDE_TOPK_MAX; an unknown perspective; cap < 0;
+ * ld_value < 1; roots and records not both set or both NULL, either not 16-B
+ * aligned; B * k >= 2^31.
+ *
+ * narde_playout_pick / narde_turn_playout_pick: per env the slot to play among
+ * its k candidates, from a playout call over the B * k roots (slot i of env e:
+ * row r = sel[e][i], sums row e * k + i, leaf row e * k + i).  The values are
+ * white's (value from a perspective-1 call).  A slot's score: r < 0 -- no
+ * candidate (score: NaN); reward[r] != 0 -- value[r], the known outcome; leaf
+ * NULL -- (float)((double)points / finished), or value[r] when no trial
+ * finished; leaf given -- (float)(((double)points + S) / trials), S the slot's
+ * non-NaN leaves added in trial order in double.  The largest score when white
+ * moves, the smallest when black does, the lowest slot on ties, NaN as the
+ * picks take it.  actions i16[B][2] / out_play i8[B][4][2] are ready for
+ * narde_step / narde_step_full: (0, 0) or the all -1 play, and row -1, for an
+ * env with no candidate.  Optional row i32[B], score f32[B][k].  Integer sums
+ * and one rounding: the same bits on every call.  NARDE_EINVAL: a NULL handle,
+ * sel, value, reward, sums, codes / play or actions / out_play; k outside
+ * 1 .. NARDE_TOPK_MAX; trials < 1; cap < 0; ld_value < 1; B * k * trials >=
+ * 2^31; codes and actions not 4-B (play and out_play not 8-B) aligned.
+ *
+ * All stream-ordered, allocate nothing, no synchronise. */
+#define NARDE_TOPK_MAX 64
+#define NARDE_RECORD_NONE_WORD6 0xFFu
+int narde_afterstates_records(narde_env *env, const uint8_t *dice, int64_t cap, int32_t *offsets,
+                              int32_t *row_env, int16_t *codes, int8_t *reward,
+                              const narde_value_mlp *net, int perspective, float *value,
+                              void *records, void *stream);
+int narde_turn_afterstates_records(narde_env *env, const uint8_t *dice, int64_t cap,
+                                   int32_t *offsets, int32_t *row_env, int8_t *play, int8_t *reward,
+                                   const narde_value_mlp *net, int perspective, float *value,
+                                   void *records, void *stream);
+int narde_rows_topk(narde_env *env, const int32_t *offsets, int64_t cap, const float *value,
+                    int64_t ld_value, int perspective, int k, const void *records, int32_t *sel,
+                    void *roots, void *stream);
+int narde_playout_pick(narde_env *env, int k, const int32_t *sel, int64_t cap, const float *value,
+                       int64_t ld_value, const int8_t *reward, const int16_t *codes, int trials,
+                       const int32_t *sums, const float *leaf, int16_t *actions, int32_t *row,
+                       float *score, void *stream);
+int narde_turn_playout_pick(narde_env *env, int k, const int32_t *sel, int64_t cap,
+                            const float *value, int64_t ld_value, const int8_t *reward,
+                            const int8_t *play, int trials, const int32_t *sums, const float *leaf,
+                            int8_t *out_play, int32_t *row, float *score, void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
  * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
