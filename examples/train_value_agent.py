@@ -13,9 +13,17 @@ section 21): K plies of self-play in one launch, then one update from the
 window with the weights held fixed over it -- truncated TD(lambda), no trace
 array; --plies is rounded up to whole windows.  The file written is the same.
 
+--playout-targets TRIALS, next to --window K, trains with
+gym_narde.td.PlayoutTargetLearner: every window's
+positions -- those of every S-th ply with --every S -- are played out TRIALS
+times to the end (--max-plies M plies at most) under the net itself, and the
+net is fitted onto the playouts' mean outcomes; with --leaf an unfinished trial
+counts at the net's value where it stopped (an M-step truncated-rollout
+target).  The file written is the same.
+
   python examples/train_value_agent.py [--envs B] [--plies N] [--hidden H] [--alpha A] [--lam L] [--epsilon E]
                                        [--rules ref2|full4] [--out-act none|sigmoid|tanh] [--seed S] [--out FILE]
-                                       [--window K]
+                                       [--window K] [--playout-targets TRIALS [--every S] [--max-plies M] [--leaf]]
 
 Play the result:  python examples/play_value_agent.py --weights FILE --fused
 """
@@ -27,32 +35,43 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 
 def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rules="ref2", out_act="tanh", seed=0,
-         out="value_agent.pt", device="cuda", report=10, window=0):
+         out="value_agent.pt", device="cuda", report=10, window=0, playout_targets=0, every=1, max_plies=400,
+         leaf=False):
     import torch
 
-    from gym_narde.td import TDLambdaLearner, WindowTDLambdaLearner
+    from gym_narde.td import PlayoutTargetLearner, TDLambdaLearner, WindowTDLambdaLearner
     from gym_narde.value_net import ValueMLP
     from gym_narde.vector import VecNardeEnv
 
     env = VecNardeEnv(envs, device=device, seed=seed, rules=rules)
     torch.manual_seed(seed)
     net = ValueMLP(hidden, "sigmoid", out_act).to(env.device)
-    if window:
+    if playout_targets and not window:
+        raise SystemExit("--playout-targets needs --window K (the plies a step plays and draws its roots from)")
+    if playout_targets:
+        learner = PlayoutTargetLearner(env, net, alpha=alpha, plies=window, trials=playout_targets, every=every,
+                                       max_plies=max_plies, leaf=leaf, epsilon=epsilon, seed=seed)
+        steps, per = -(-plies // window), window
+    elif window:
         learner = WindowTDLambdaLearner(env, net, alpha=alpha, lam=lam, plies=window, epsilon=epsilon, seed=seed)
         steps, per = -(-plies // window), window
     else:
         learner = TDLambdaLearner(env, net, alpha=alpha, lam=lam, epsilon=epsilon, seed=seed)
         steps, per = plies, 1
     print(f"{envs} envs, hidden {hidden}, out {out_act}: learner memory {learner.memory_bytes() / 1e6:.1f} MB")
-    every = max(1, steps // max(1, report))
+    period = max(1, steps // max(1, report))
     err = torch.zeros((), device=env.device)
     for step in range(steps):
-        delta = learner.step()[-1]
-        err += delta.abs().mean()
-        if (step + 1) % every == 0 or step + 1 == steps:
-            n = (step % every) + 1
+        if playout_targets:  # the root-mean-square error against the playout targets
+            loss = learner.step()[0]
+            err += (loss[0] / loss[1].clamp(min=1.0)).sqrt().float()
+        else:
+            err += learner.step()[-1].abs().mean()
+        if (step + 1) % period == 0 or step + 1 == steps:
+            n = (step % period) + 1
             ep = int(env.stats().sum(0)[0])
-            print(f"ply {(step + 1) * per}: mean |delta| {float(err) / n:.4f}, {ep} games finished")
+            what = "rms error" if playout_targets else "mean |delta|"
+            print(f"ply {(step + 1) * per}: {what} {float(err) / n:.4f}, {ep} games finished")
             err.zero_()
     torch.save(net.state_dict(), out)
     print(f"saved {out}")
@@ -73,5 +92,11 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default="value_agent.pt")
     ap.add_argument("--window", type=int, default=0, help="K > 0: windowed TD(lambda), K plies a launch and update")
+    ap.add_argument("--playout-targets", type=int, default=0, metavar="TRIALS",
+                    help="TRIALS > 0 (with --window K): fit the net onto playouts of each window's positions")
+    ap.add_argument("--every", type=int, default=1, help="playout roots: the positions of every S-th ply of a window")
+    ap.add_argument("--max-plies", type=int, default=400, help="a playout trial's length bound")
+    ap.add_argument("--leaf", action="store_true", help="count an unfinished trial at the net's value where it stopped")
     a = ap.parse_args()
-    main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out, window=a.window)
+    main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out, window=a.window,
+         playout_targets=a.playout_targets, every=a.every, max_plies=a.max_plies, leaf=a.leaf)

@@ -49,6 +49,12 @@
 //                       k_rows_topk, k_playout_pick)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
+//   kernels_td_window.h  windowed TD(lambda): the window's values, returns and
+//                       slab gradient sums (k_tdw_values, k_tdw_returns,
+//                       k_tdw_grad)
+//   kernels_value_fit.h  the supervised fit of given records to given float
+//                       targets, and the playout targets (k_fit_grad,
+//                       k_fit_loss, k_playout_targets)
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip);
 // host_common.h: the host helpers the two share.
@@ -86,6 +92,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_playout_pick.h"
 #include "kernels_td.h"
 #include "kernels_td_window.h"
+#include "kernels_value_fit.h"
 
 namespace {
 
@@ -1266,6 +1273,65 @@ int narde_value_td_window(narde_env* e, const narde_value_mlp_train* net, int pl
   if (const int rc = check_launch("k_tdw_grad")) return rc;
   k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
   return check_launch("k_td_update");
+}
+
+int narde_value_fit(int device, const narde_value_mlp_train* net, int64_t n, const void* records, const float* target,
+                    const float* weight, float alpha, float* scratch, int64_t scratch_floats, float* v, double* loss,
+                    void* stream) {
+  if (!net || !records || !target || !scratch) return fail(NARDE_EINVAL, "NULL argument");
+  if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
+  if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
+                                      net->out_act, kValLdMax))
+    return rc;
+  if (net->w1 && net->ld_w1 < 198) return fail(NARDE_EINVAL, "ld_w1 %lld below 198", (long long)net->ld_w1);
+  if (n < 1 || n >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "n %lld outside 1 .. 2^31 - 1", (long long)n);
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  if (reinterpret_cast<uintptr_t>(loss) & 7u) return fail(NARDE_EINVAL, "loss must be 8-B aligned");
+  const int64_t need = fit_scratch_floats(n, net->hidden);
+  if (scratch_floats < need)
+    return fail(NARDE_EINVAL, "scratch_floats %lld below NARDE_VALUE_FIT_SCRATCH_FLOATS = %lld",
+                (long long)scratch_floats, (long long)need);
+  const TdNet tn{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->w1, net->ld_w1, net->hidden, net->hidden_act,
+                 net->out_act};
+  DeviceGuard dg(device);
+  hipStream_t st = (hipStream_t)stream;
+  // k_fit_grad's accumulator, as k_tdw_grad's, is past the 64 KB a launch may ask for unannounced from hidden = 82
+  // on: once a device
+  static std::atomic<uint64_t> announced{0};
+  const uint64_t bit = uint64_t(1) << (device & 63);
+  if (!(announced.load(std::memory_order_relaxed) & bit)) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_fit_grad), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)(td_row_floats(kValHiddenMax) * sizeof(float))));
+    announced.fetch_or(bit, std::memory_order_relaxed);
+  }
+  const int slabs = (int)tdw_slabs(n);
+  const int64_t P = td_row_floats(tn.hidden), ld_part = P + 3;
+  float* part = scratch;
+  double* slab_loss = reinterpret_cast<double*>(scratch + slabs * ld_part);  // (ld_part: whole float4s)
+  k_fit_grad<<<(unsigned)slabs, 2 * kTdBlock, (size_t)P * sizeof(float), st>>>((const uint4*)records, n, tn, target, weight,
+                                                                           part, ld_part, slab_loss, v);
+  if (const int rc = check_launch("k_fit_grad")) return rc;
+  k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
+  if (const int rc = check_launch("k_td_update")) return rc;
+  if (!loss) return NARDE_OK;
+  k_fit_loss<<<1, 64, 0, st>>>(slab_loss, slabs, loss);
+  return check_launch("k_fit_loss");
+}
+
+int narde_playout_targets(int device, int64_t n, int trials, const int32_t* sums, const float* leaf, const void* roots,
+                          float* target, float* weight, void* stream) {
+  if (!sums || !target || !weight) return fail(NARDE_EINVAL, "NULL argument");
+  if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
+  if (n < 1 || n >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "n %lld outside 1 .. 2^31 - 1", (long long)n);
+  if (trials < 1) return fail(NARDE_EINVAL, "trials %d below 1", trials);
+  if (n * (int64_t)trials >= (int64_t(1) << 31))
+    return fail(NARDE_EINVAL, "n x trials = %lld: 2^31 or more", (long long)(n * (int64_t)trials));
+  if (!aligned16(roots)) return fail(NARDE_EINVAL, "roots must be 16-B aligned");
+  DeviceGuard dg(device);
+  k_playout_targets<<<grid(n), kBlock, 0, (hipStream_t)stream>>>(n, trials, sums, leaf, (const uint32_t*)roots, target,
+                                                                 weight);
+  return check_launch("k_playout_targets");
 }
 
 int narde_turn_pick(narde_env* e, const int32_t* offsets, const int8_t* play, int64_t cap, const float* value,

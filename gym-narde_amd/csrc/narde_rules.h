@@ -2821,4 +2821,53 @@ NARDE_FN int playout_pick_slot(const int32_t* sel, int k, int64_t cap, const flo
   return bi;
 }
 
+// ------------------------------------------- the value MLP's supervised fit
+// narde_value_fit's and narde_playout_targets' arithmetic (kernels_value_fit.h;
+// the host check tests/hostcheck/hostcheck_value_fit.cpp runs the same
+// functions in the kernels' order).  The gradient sum is the windowed update's:
+// kFitSlab samples a partial row, tdw_acc / tdw_acc_b2 in sample order.
+constexpr int kFitSlab = kTdwSlab;
+// Sample i's weight on its gradient, G, from its value v: without weights the
+// error e = target - v (one subtraction); with them w e, and for w == 0 exactly
+// 0 with the target never read.  w and e are what the loss takes.
+NARDE_FN float fit_gain(const float* target, const float* weight, int64_t i, float v, float& w, float& e) {
+  w = weight ? weight[i] : 1.0f;
+  e = 0.0f;
+  if (weight && w == 0.0f) return 0.0f;
+  e = target[i] - v;
+  return weight ? w * e : e;
+}
+// a slab's loss {sum w e^2, sum w} in double, a sample at a time in sample
+// order; a zero weight adds nothing.  Three roundings a sample, none fused:
+// w e, (w e) e, the add.
+NARDE_FN void fit_loss_add(double& se, double& sw, float w, float e) {
+#pragma clang fp contract(off)
+  if (w == 0.0f) return;
+  const double we = (double)w * (double)e;
+  const double wee = we * (double)e;
+  se = se + wee;
+  sw = sw + (double)w;
+}
+// scratch: the partial rows, td_row_floats + 3 floats each, then a slab's loss
+// as two doubles (4 floats) each; nothing per sample
+NARDE_FN int64_t fit_scratch_floats(int64_t n, int hidden) { return tdw_slabs(n) * (td_row_floats(hidden) + 3 + 4); }
+
+// A playout root's regression target and weight from its sums {finished,
+// points, squares, plies} (playout_slot_score's arithmetic: the bits are the
+// pick's score).  Without leaves the mean outcome of the finished trials, and
+// weight 0 when none finished; with leaves the truncated mean over all trials.
+// root (optional): the root's 8-word record -- one in which a side has its 15
+// checkers off (a terminal row's, the none record) is no position of a game:
+// target 0, weight 0.
+NARDE_FN void playout_target(const int32_t* sums, const float* leaf, int trials, const uint32_t* root, float& target,
+                             float& weight) {
+  const bool over = root && ((root[6] & 15u) == 15u || ((root[6] >> 4) & 15u) == 15u);
+  if (over || (!leaf && sums[0] <= 0)) {
+    target = weight = 0.0f;
+    return;
+  }
+  target = playout_slot_score(0, 0.0f, sums, leaf, trials);
+  weight = 1.0f;
+}
+
 }  // namespace narde

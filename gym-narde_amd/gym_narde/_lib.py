@@ -36,6 +36,15 @@ def td_window_scratch_floats(num_envs, plies, hidden):
             + (k * b + TD_WINDOW_SLAB - 1) // TD_WINDOW_SLAB * (200 * int(hidden) + 4))
 
 
+VALUE_FIT_SLAB = TD_WINDOW_SLAB  # NARDE_VALUE_FIT_SLAB
+
+
+def value_fit_scratch_floats(n, hidden):
+    """NARDE_VALUE_FIT_SCRATCH_FLOATS: narde_value_fit's scratch (a partial
+    row and two doubles a slab)."""
+    return (int(n) + VALUE_FIT_SLAB - 1) // VALUE_FIT_SLAB * (200 * int(hidden) + 4 + 4)
+
+
 def lookahead_scratch_bytes(cap):
     """NARDE_LOOKAHEAD_SCRATCH_BYTES: narde_afterstates_lookahead's scratch."""
     return 32 * int(cap)
@@ -152,6 +161,9 @@ SIGNATURES = {
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),
     "narde_value_td_window": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
                                      ctypes.c_float, ctypes.c_float, _vp, _i64, _vp, _vp]),
+    "narde_value_fit": (_i32, [_i32, ctypes.POINTER(ValueMlpTrain), _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _i64, _vp,
+                               _vp, _vp]),
+    "narde_playout_targets": (_i32, [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

@@ -25,6 +25,14 @@ over it,
     G_k = delta_k + gamma lam G_{k+1} (cut where an episode ended, G_K = 0).
 It keeps no trace array.  It is truncated TD(lambda), not the online
 learner's algorithm: no credit crosses a window's left edge.
+
+ValueFitter is the supervised layer: one update that
+regresses given records onto given float targets (narde_value_fit) -- playout
+means, lookahead values, anything a caller can compute for a position --,
+    theta <- theta + alpha sum_i w_i (target_i - v(s_i)) grad_theta v(s_i).
+PlayoutTargetLearner closes the loop with it: a window of self-play, Monte-Carlo
+playouts of the window's positions (VecNardeEnv.playout), their means as the
+targets (VecNardeEnv.playout_targets), one fit.
 """
 import ctypes
 
@@ -120,6 +128,161 @@ class WindowTDLambdaLearner:
         if self._roll_scratch is not None:
             own.append(self._roll_scratch)
         return sum(x.numel() * x.element_size() for x in own)
+
+
+class ValueFitter:
+    """A supervised fit of a ValueMLP on given records and given float
+    targets, on the device (narde_value_fit).  env: a VecNardeEnv (its device
+    and stream; its positions are not touched); net: a ValueMLP on that
+    device; n: the most samples a call takes.  Owns the scratch and the train
+    struct; after a step net(feat), state_dict() and scored_afterstates(net)
+    agree with no pack(), as with the TD learners."""
+
+    def __init__(self, env, net, n):
+        t = env.torch
+        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+            raise TypeError("ValueFitter needs a gym_narde.value_net.ValueMLP")
+        if net.l1.weight.device != env.device:
+            raise ValueError(f"the net is on {net.l1.weight.device}, the env on {env.device}")
+        if int(n) < 1:
+            raise ValueError("n must be >= 1")
+        self.env, self.net, self.n = env, net, int(n)
+        z = dict(device=env.device)
+        self.scratch = t.empty(_lib.value_fit_scratch_floats(self.n, net.hidden), dtype=t.float32, **z)
+        self.v = t.zeros(self.n, dtype=t.float32, **z)
+        self.loss = t.zeros(2, dtype=t.float64, **z)
+        self._m = 0
+        self._mlp = _train_struct(env, net)
+
+    def step(self, records, target, weight=None, *, alpha):
+        """theta += alpha sum_i w_i (target_i - v(s_i)) grad v(s_i): a sum, not
+        a mean (divide alpha by the weights' sum for that).  records (m, 8)
+        int32 (state_records(), a records rollout's, recorded rows'), m <= n;
+        target (m,) float32 white's values to regress to; weight (m,) float32
+        or None (all 1) -- where it is 0 the target is never read.  Returns
+        the device tensor loss (2,) float64 = (sum w e^2, sum w) under the
+        weights the call found (the fitter's own, rewritten by the next call).
+        No synchronise."""
+        t, env = self.env.torch, self.env
+        if (not isinstance(records, t.Tensor) or records.dtype != t.int32 or records.device != env.device
+                or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8):
+            raise ValueError("records must be a contiguous (m, 8) int32 device tensor")
+        m = int(records.shape[0])
+        if not 1 <= m <= self.n:
+            raise ValueError(f"{m} samples: the fitter was made for 1 .. {self.n}")
+        target = env._dev(target, t.float32, (m,))
+        weight = None if weight is None else env._dev(weight, t.float32, (m,))
+        _lib.check(env.handle.lib.narde_value_fit(env.device.index, ctypes.byref(self._mlp), m, _lib.ptr(records),
+                                                  _lib.ptr(target), _lib.ptr(weight), float(alpha),
+                                                  _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.v),
+                                                  _lib.ptr(self.loss), env._s()), "narde_value_fit")
+        self._m, self._keep = m, (records, target, weight)
+        return self.loss
+
+    def evaluate(self, records, target, weight=None):
+        """step() with alpha = 0: the loss and values(), no weight bit moved."""
+        return self.step(records, target, weight, alpha=0.0)
+
+    def values(self):
+        """v (m,) of the last call: v(s_i) under the weights it found."""
+        return self.v[:self._m]
+
+    def memory_bytes(self):
+        """Device memory the fitter owns."""
+        return sum(x.numel() * x.element_size() for x in (self.scratch, self.v, self.loss))
+
+
+class PlayoutTargetLearner:
+    """Self-play, playouts of its positions, a fit onto their means (DESIGN.md
+    section 24).  env: a VecNardeEnv (either rule set) with autoreset; net: a
+    ValueMLP on its device.  Every step: play() -- `plies` plies of
+    value-greedy self-play in one launch that records each ply's position;
+    targets() -- the positions of plies k % every == 0, N = ceil(plies / every)
+    * B roots, each played out `trials` times to the end (max_plies plies at
+    most) under playout_net on both colours (None: the net itself), the roots'
+    mean outcomes the targets; update() -- one narde_value_fit of those roots
+    at step size alpha (a sum over the roots).  Without leaf a root none of
+    whose trials finished gets weight 0.  With leaf=True an unfinished trial
+    counts at the net's value of the position it stopped at: with a small
+    max_plies that is an n-step truncated-rollout target, a bootstrap max_plies
+    plies deep instead of a Monte-Carlo return.  epsilon: the explore
+    probability of the self-play (None: greedy); common_dice: playout()'s.
+    The playouts' seed is seed + the count of windows played: the same
+    arguments and the same number of steps give the same weight bits."""
+
+    def __init__(self, env, net, alpha, plies, trials, every=1, max_plies=400, leaf=False, playout_net=None,
+                 epsilon=None, common_dice=False, seed=0):
+        t = env.torch
+        _check_learner("PlayoutTargetLearner", env, net, 0.0)
+        if int(plies) < 1 or int(trials) < 1 or int(every) < 1 or int(max_plies) < 1:
+            raise ValueError("plies, trials, every and max_plies must be >= 1")
+        self.env, self.net, self.plies, self.trials = env, net, int(plies), int(trials)
+        self.every, self.max_plies, self.leaf = int(every), int(max_plies), bool(leaf)
+        self.playout_net = net if playout_net is None else playout_net
+        self.alpha, self.seed, self.common_dice = float(alpha), int(seed), bool(common_dice)
+        self.windows = 0
+        z = dict(device=env.device)
+        B, M = env.num_envs, -(-self.plies // self.every)
+        N = M * B
+        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
+        self.bufs = make(self.plies, records=True)
+        self.roots = t.zeros((N, 8), dtype=t.int32, **z)
+        self.result = None  # the playouts' PlayoutResult, made by the first targets()
+        self.target = t.zeros(N, dtype=t.float32, **z)
+        self.weight = t.zeros(N, dtype=t.float32, **z)
+        self.fitter = ValueFitter(env, net, N)
+        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
+        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
+        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
+
+    def play(self):
+        """The window's plies in one launch, the net on both sides; the
+        explore tag advances by them.  Returns the launch's buffers."""
+        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
+        if env.full:
+            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
+        else:
+            env.value_rollout(self.plies, self.net, **kw)
+        if self._tag is not None:
+            self._tag += self.plies
+        self.windows += 1
+        return self.bufs
+
+    def targets(self):
+        """Playouts of the window's positions and their targets.  Returns
+        (target, weight), each (N,), root j * B + e = env e before ply j *
+        every (the learner's own buffers)."""
+        env, B = self.env, self.env.num_envs
+        self.roots.view(-1, B, 8).copy_(self.bufs["records"][::self.every])
+        self.result = env.playout(self.roots, self.trials, self.playout_net, max_plies=self.max_plies,
+                                  seed=self.seed + self.windows, common_dice=self.common_dice, leaf=self.leaf,
+                                  out=self.result)
+        return env.playout_targets(self.result, roots=self.roots, leaf=self.leaf, out=(self.target, self.weight))
+
+    def update(self):
+        """One fit of the roots onto targets()' numbers.  Returns the loss
+        (2,) float64 = (sum w e^2, sum w) under the weights it found."""
+        return self.fitter.step(self.roots, self.target, self.weight, alpha=self.alpha)
+
+    def step(self):
+        """play(), targets(), update().  Returns (loss, target, weight)."""
+        self.play()
+        self.targets()
+        return self.update(), self.target, self.weight
+
+    def values(self):
+        """v (N,) of the last update, under the weights it found."""
+        return self.fitter.values()
+
+    def memory_bytes(self):
+        """Device memory the learner owns."""
+        own = [x for x in self.bufs.values() if x is not None] + [self.roots, self.target, self.weight]
+        if self.result is not None:
+            own += [x for x in (self.result.sums, self.result.outcome, self.result.length, self.result.leaf)
+                    if x is not None]
+        if self._roll_scratch is not None:
+            own.append(self._roll_scratch)
+        return sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
 
 
 class TDLambdaLearner:

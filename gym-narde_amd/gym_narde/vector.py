@@ -1140,6 +1140,47 @@ class VecNardeEnv:
         self._keep = (roots, net_white, net_black, structs, out, scratch)
         return out
 
+    def playout_targets(self, result, roots=None, leaf=False, out=None):
+        """A playout call's sums as regression targets for td.ValueFitter
+        (narde_playout_targets), by pick_playout()'s
+        score arithmetic: per root the mean outcome of its finished trials
+        and weight 1 -- target 0 and weight 0 where none finished --, or with
+        leaf=True the truncated mean (points + the unfinished trials' leaves)
+        / trials and weight 1.  result: playout()'s PlayoutResult or a (sums,
+        trials[, leaf]) tuple.  roots: the (N, 8) records the playouts started
+        from; given, a root in which a side already has its 15 checkers off
+        (a terminal row's record, the none record) gets target 0, weight 0.
+        Returns (target, weight), (N,) float32; out: an earlier pair to write
+        into.  No synchronise."""
+        t = self.torch
+        if isinstance(result, PlayoutResult):
+            sums, trials, lf = result.sums, result.trials, result.leaf
+        else:
+            sums, trials = result[0], int(result[1])
+            lf = result[2] if len(result) > 2 else None
+        if leaf and lf is None:
+            raise ValueError("leaf=True needs the playouts' leaf values (playout(leaf=True))")
+        lf = lf if leaf else None
+        if (sums.dim() != 2 or sums.shape[1] != 4 or sums.shape[0] < 1 or sums.dtype != t.int32
+                or not sums.is_contiguous() or sums.device != self.device):
+            raise ValueError("result must hold (N, 4) int32 sums on this device")
+        N = int(sums.shape[0])
+        if lf is not None and (tuple(lf.shape) != (N, trials) or lf.dtype != t.float32 or not lf.is_contiguous()):
+            raise ValueError("leaf must be (N, trials) float32")
+        if roots is not None and (tuple(roots.shape) != (N, 8) or roots.dtype != t.int32 or not roots.is_contiguous()
+                                  or roots.device != self.device):
+            raise ValueError("roots must be the playouts' contiguous (N, 8) int32 records")
+        if out is not None:
+            target, weight = out
+        else:
+            target = t.empty(N, dtype=t.float32, device=self.device)
+            weight = t.empty(N, dtype=t.float32, device=self.device)
+        _lib.check(self.handle.lib.narde_playout_targets(self.device.index, N, trials, _lib.ptr(sums), _lib.ptr(lf),
+                                                         _lib.ptr(roots), _lib.ptr(target), _lib.ptr(weight), self._s()),
+                   "narde_playout_targets")
+        self._keep = (sums, lf, roots)
+        return target, weight
+
     def rollout_launcher(self, plies, bufs, events=None, totals=None):
         """rollout(plies, bufs) pre-bound: a zero-argument callable that makes
         exactly one ctypes call (one kernel launch on the stream current

@@ -861,6 +861,62 @@ int narde_value_td_window(narde_env *env, const narde_value_mlp_train *net, int 
                           const uint8_t *truncated, float alpha, float lam, float gamma,
                           float *scratch, int64_t scratch_floats, float *delta, void *stream);
 
+/* A supervised fit of that value MLP: one weight update that regresses given
+ * records onto given float targets -- playout means,
+ * lookahead values, anything a caller can compute for a position.  Stateless:
+ * a device, no handle.  records u32[n][8], 16-B aligned, in the layout the
+ * records rollouts and narde_state_records write; target f32[n] white's value
+ * to regress to; weight f32[n] or NULL (all 1).  Under the weights as they
+ * are on entry:
+ *   v_i = v(records[i]), white's value, written to v f32[n] if not NULL;
+ *   weight NULL: e_i = target_i - v_i (one float subtraction), G_i = e_i;
+ *   weight given: G_i = 0 exactly where w_i == 0 -- target_i is then never
+ *                 read and may be NaN --, w_i * e_i elsewhere;
+ * then theta += alpha * sum_i G_i * grad_theta v(records[i]) into w1t, b1, w2,
+ * b2 and the mirror, the same bits to both: a sum, not a mean.  alpha == 0
+ * with finite inputs leaves every weight bit as it was (a validation loss).
+ * loss f64[2] (8-B aligned) or NULL = {sum w_i e_i^2, sum w_i}: per slab, in
+ * sample order, in double -- (double)w * (double)e * (double)e, w = 1 without
+ * weights, a zero-weight sample adding nothing --, then the slabs in slab
+ * order.
+ * The gradient sum has narde_value_td_window's order and no float atomics --
+ * the samples in index order in slabs of NARDE_VALUE_FIT_SLAB
+ * (= NARDE_TD_WINDOW_SLAB), every element of a slab's partial row taking its
+ * addends in sample order, then the partial rows in slab order --: the same
+ * inputs give the same bits, and a window whose every ply is terminated gives
+ * narde_value_td_window's bits when its outcomes are the targets.  One
+ * forward a sample: no values pass, no returns pass, no v or G read back.
+ * scratch: device memory, 16-B aligned, scratch_floats >=
+ * NARDE_VALUE_FIT_SCRATCH_FLOATS(n, hidden): a partial row and two doubles a
+ * slab, nothing per sample; its contents on return are unspecified.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable once
+ * the device has seen one call (the first announces the gradient kernel's
+ * LDS).  NARDE_EINVAL before any device call: narde_value_td_trace's net
+ * cases, a NULL net, records, target or scratch, a negative device, n < 1 or
+ * n >= 2^31, records or scratch not 16-B aligned, scratch too small, loss not
+ * 8-B aligned.
+ *
+ * narde_playout_targets: a playout call's sums i32[n][4] (and its leaf
+ * f32[n][trials], or NULL) as regression targets, by narde_playout_pick's
+ * score arithmetic (the same bits).  Per root: leaf NULL -- target =
+ * (float)((double)points / finished) and weight 1, or target 0 and weight 0
+ * when no trial finished; leaf given -- target = (float)(((double)points + S)
+ * / trials), S the non-NaN leaves added in trial order in double, weight 1.
+ * roots u32[n][8] (16-B aligned) or NULL: a root in which a side already has
+ * its 15 checkers off -- a terminal row's record, the none record -- is no
+ * position of a game and gets target 0, weight 0.  NARDE_EINVAL before any
+ * device call: a NULL sums, target or weight, a negative device, n < 1 or
+ * n >= 2^31, trials < 1, n * trials >= 2^31, roots not 16-B aligned. */
+#define NARDE_VALUE_FIT_SLAB NARDE_TD_WINDOW_SLAB
+#define NARDE_VALUE_FIT_SCRATCH_FLOATS(n, hidden)                                      \
+  ((((int64_t)(n) + NARDE_VALUE_FIT_SLAB - 1) / NARDE_VALUE_FIT_SLAB) *                \
+   (200 * (int64_t)(hidden) + 4 + 4))
+int narde_value_fit(int device, const narde_value_mlp_train *net, int64_t n, const void *records,
+                    const float *target, const float *weight, float alpha, float *scratch,
+                    int64_t scratch_floats, float *v, double *loss, void *stream);
+int narde_playout_targets(int device, int64_t n, int trials, const int32_t *sums, const float *leaf,
+                          const void *roots, float *target, float *weight, void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry
