@@ -1,7 +1,7 @@
 """Random positions for differential tests (test_gpu_fuzz.py,
-test_full4_cpu.py, test_gpu_afterstate_fuzz.py): run-heavy boards where the
-block rule decides and bear-off endgames, placed for a random mover.  Test
-helper, not a test."""
+test_full4_cpu.py, test_gpu_afterstate_fuzz.py, test_rollout_fuzz_cpu.py,
+test_gpu_rollout_fuzz.py): run-heavy boards where the block rule decides and
+bear-off endgames, placed for a random mover.  Test helper, not a test."""
 import numpy as np
 from test_oracle_golden import _prime_boards
 
@@ -75,6 +75,38 @@ def turn_states(n, seed, doubles=0.5):
                 take -= c
                 off[i, 0 if opp == 1 else 1] += c
     return dict(board=board, off=off, ft=ft, player=player, dice=dice)
+
+
+def first_rolls(n, seed, env0):
+    """The roll each of the ids env0 .. env0 + n - 1 sees at ply counter 0
+    under the device's dice stream of `seed`, from the oracle: (n, 2) uint8.
+    It depends on the seed, the id and the counter, not on the position."""
+    import oracle as O
+
+    sp = O.SelfPlay(n, seed, env0)
+    sp.reset(0)
+    return sp.run(1)["dice"][0].copy()
+
+
+def place_for_rolls(st, first):
+    """A turn_states(n, seed) set permuted for ids that draw their own dice
+    (the one-launch rollouts and the playouts): the run-heavy half, in its
+    order, goes first to the ids that roll a double -- `first` is the ids'
+    (n, 2) first rolls, or (n, trials, 2) where an id is a playout root of
+    several trials: one double among them is enough -- in ascending order, and
+    every other position, in the set's order, to the ids left.  Returns the
+    dict of turn_states(), the dice column the ids' own (trial 0's)."""
+    first = np.asarray(first, np.uint8)
+    n = len(st["player"])
+    rolls = first.reshape(n, -1, 2)
+    dbl = (rolls[:, :, 0] == rolls[:, :, 1]).any(1)
+    ids = np.concatenate([np.flatnonzero(dbl), np.flatnonzero(~dbl)])
+    src = np.empty(n, np.int64)
+    src[ids] = np.arange(n)  # position k of the set sits at id ids[k]
+    out = {k: np.ascontiguousarray(np.asarray(st[k])[src]) for k in ("board", "off", "ft", "player")}
+    out["dice"] = np.ascontiguousarray(rolls[:, 0])
+    out["heavy"] = src < n // 2  # which ids hold a position of the run-heavy half
+    return out
 
 
 def spread_replier_states(n, seed):

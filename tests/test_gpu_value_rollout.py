@@ -24,7 +24,7 @@ import pytest
 import oracle as O
 from conftest import ROOT
 from test_value_cpu import make_net
-from test_value_rollout_cpu import M32, endgames, judge
+from test_value_rollout_cpu import M32, endgames, judge, mulhi
 
 pytestmark = pytest.mark.gpu
 
@@ -80,7 +80,8 @@ def replay(env2, bufs, plies, gw, cw, gb, cb, eps=None, max_steps=1000):
     """Walk env2 through the recorded plies with the existing calls."""
     B = env2.num_envs
     J = dict(gap=[], is_best=[], short=[], verr=[], e32=0.0, mag=0.0, norow=0, explored=0, random=0, greedy=0,
-             value_bits_equal=0, action_equals_pick=0, terminal_pick=0, resets=0)
+             value_bits_equal=0, action_equals_pick=0, terminal_pick=0, resets=0, most_rows=0, greedy_above_64=0,
+             above_256=0, explore_ordinal_64=0)
     out = {k: np_(v) for k, v in bufs.items() if v is not None}
     eps_q = None if eps is None else int(float(np.float32(eps)) * 4294967296.0)
     for k in range(plies):
@@ -131,6 +132,8 @@ def replay(env2, bufs, plies, gw, cw, gb, cb, eps=None, max_steps=1000):
                 assert got == tuple(int(x) for x in rand_act[e]) and np.isnan(val), f"ply {k} env {e}: random ply"
                 continue
             r0, r1 = int(offs[e]), int(offs[e + 1])
+            J["most_rows"] = max(J["most_rows"], r1 - r0)
+            J["above_256"] += int(r1 - r0 > 256)
             if r1 == r0:
                 J["norow"] += 1
                 assert got == (0, 0) and np.isnan(val), f"ply {k} env {e}: no row"
@@ -152,9 +155,11 @@ def replay(env2, bufs, plies, gw, cw, gb, cb, eps=None, max_steps=1000):
                 explore = r[0] < eps_q
             if explore:
                 J["explored"] += 1
+                J["explore_ordinal_64"] += int(mulhi(r[1], r1 - r0) >= 64)  # the drawn row is not in the first chunk
                 assert got == tuple(int(x) for x in pick_act[e]) and pick_row[e] == r0 + j, f"ply {k} env {e}: explore"
                 continue
             J["greedy"] += 1
+            J["greedy_above_64"] += int(r1 - r0 > 64)  # a second 64-row chunk
             jb = int(np.argmax(x64))
             rest = np.delete(x64, jb)
             J["gap"].append(float(x64[jb] - rest.max()) if len(rest) else np.inf)
