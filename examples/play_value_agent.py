@@ -14,7 +14,10 @@ search -- every afterstate is valued by the expectation, over the opponent's
 rolls, of the opponent's best reply under the same net (value_play's
 LookaheadPlayer: lookahead_afterstates, --rules full4:
 lookahead_turn_afterstates over whole-turn replies; --plies is already the
-number of plies played).  --one-launch (depth 1; implies --fused): the
+number of plies played).  --depth 2 --top K: the pruned search -- only each
+env's K best rows by one-ply value are searched, and the best of those by
+two-ply value is played (LookaheadPlayer(top=K): recorded_afterstates ->
+top_rows -> lookahead_records -> pick_slots -> step).  --one-launch (depth 1; implies --fused): the
 --plies plies are one launch (VecNardeEnv.value_rollout, --rules full4:
 turn_value_rollout), the same games.  --playout TRIALS [--top K] (either rule
 set, implies --fused): playout-greedy play -- each env's K best rows by one-ply
@@ -22,7 +25,7 @@ value are played out TRIALS times to the end under the same net and the best
 mean outcome is played (value_play's PlayoutPlayer: recorded_afterstates ->
 top_rows -> playout -> pick_playout -> step).
 
-  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2] [--one-launch] [--playout TRIALS [--top K]]
+  python examples/play_value_agent.py [--envs B] [--plies N] [--seed S] [--epsilon E] [--weights FILE] [--rules ref2|full4] [--fused] [--depth 1|2 [--top K]] [--one-launch] [--playout TRIALS [--top K]]
 """
 import argparse
 import os
@@ -43,7 +46,7 @@ def make_net(seed, device):
 
 
 def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda", rules="ref2", fused=False, depth=1,
-         one_launch=False, playout=0, top=4):
+         one_launch=False, playout=0, top=None):
     import torch
 
     from gym_narde.value_play import LookaheadPlayer, PlayoutPlayer, ValuePlayer
@@ -66,7 +69,11 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         from gym_narde.value_net import ValueMLP
 
         net = ValueMLP.from_sequential(net)
-    player = LookaheadPlayer(env, net) if depth == 2 else ValuePlayer(env, net, perspective="white")
+    if top is not None and depth == 2 and epsilon > 0:
+        raise ValueError("--depth 2 --top K plays greedily, without --epsilon")
+    if top is not None and depth != 2 and not playout:
+        raise ValueError("--top goes with --depth 2 or --playout")
+    player = (LookaheadPlayer(env, net, top=top) if depth == 2 else ValuePlayer(env, net, perspective="white"))
     eps = torch.tensor(epsilon, dtype=torch.float32, device=env.device) if epsilon > 0 else None
     if one_launch:
         rollout = env.turn_value_rollout if env.full else env.value_rollout
@@ -76,6 +83,7 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         env.close()
         return ep, white, black
     if playout:
+        top = 4 if top is None else top
         player = PlayoutPlayer(env, net, k=top, trials=playout, seed=seed)
         rows = played = 0
         for ply in range(plies):
@@ -94,7 +102,8 @@ def main(envs=1024, plies=200, seed=0, epsilon=0.0, weights=None, device="cuda",
         _, _, _, _, _, aft, _, _ = player.step(epsilon=eps, tag=tag, seed=seed)
         rows += aft.cap
     ep, white, black = (int(x) for x in env.stats().sum(0).tolist())
-    print(f"{envs} envs x {plies} plies: {rows / (envs * plies):.1f} afterstates per roll, {ep} games finished, "
+    pruned = f", the best {top} searched two plies deep" if depth == 2 and top is not None else ""
+    print(f"{envs} envs x {plies} plies: {rows / (envs * plies):.1f} afterstates per roll{pruned}, {ep} games finished, "
           f"points white {white} / black {black}")
     env.close()
     return ep, white, black
@@ -115,7 +124,9 @@ if __name__ == "__main__":
                     help="play the plies in one launch (value_rollout, full4: turn_value_rollout; depth 1)")
     ap.add_argument("--playout", type=int, default=0, metavar="TRIALS",
                     help="playout-greedy play: TRIALS playouts of each of the best --top rows (ref2 and full4)")
-    ap.add_argument("--top", type=int, default=4, metavar="K", help="the candidates a roll's playouts choose among")
+    ap.add_argument("--top", type=int, default=None, metavar="K",
+                    help="the candidates a roll's playouts choose among (default 4); with --depth 2: search only the "
+                         "K best rows by one-ply value (default: all)")
     a = ap.parse_args()
     main(a.envs, a.plies, a.seed, a.epsilon, a.weights, rules=a.rules, fused=a.fused, depth=a.depth,
          one_launch=a.one_launch, playout=a.playout, top=a.top)

@@ -21,9 +21,16 @@ net is fitted onto the playouts' mean outcomes; with --leaf an unfinished trial
 counts at the net's value where it stopped (an M-step truncated-rollout
 target).  The file written is the same.
 
+--lookahead-targets, next to --window K, trains with
+gym_narde.td.LookaheadTargetLearner: every window's
+positions (--every S as above) are valued two plies deep under the net itself
+-- the expectation, over the mover's rolls, of the mover's best afterstate --
+and the net is fitted onto those values.  The file written is the same.
+
   python examples/train_value_agent.py [--envs B] [--plies N] [--hidden H] [--alpha A] [--lam L] [--epsilon E]
                                        [--rules ref2|full4] [--out-act none|sigmoid|tanh] [--seed S] [--out FILE]
                                        [--window K] [--playout-targets TRIALS [--every S] [--max-plies M] [--leaf]]
+                                       [--lookahead-targets [--every S]]
 
 Play the result:  python examples/play_value_agent.py --weights FILE --fused
 """
@@ -36,10 +43,10 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rules="ref2", out_act="tanh", seed=0,
          out="value_agent.pt", device="cuda", report=10, window=0, playout_targets=0, every=1, max_plies=400,
-         leaf=False):
+         leaf=False, lookahead_targets=False):
     import torch
 
-    from gym_narde.td import PlayoutTargetLearner, TDLambdaLearner, WindowTDLambdaLearner
+    from gym_narde.td import LookaheadTargetLearner, PlayoutTargetLearner, TDLambdaLearner, WindowTDLambdaLearner
     from gym_narde.value_net import ValueMLP
     from gym_narde.vector import VecNardeEnv
 
@@ -48,7 +55,13 @@ def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rul
     net = ValueMLP(hidden, "sigmoid", out_act).to(env.device)
     if playout_targets and not window:
         raise SystemExit("--playout-targets needs --window K (the plies a step plays and draws its roots from)")
-    if playout_targets:
+    if lookahead_targets and (not window or playout_targets):
+        raise SystemExit("--lookahead-targets needs --window K and excludes --playout-targets")
+    fitted = bool(playout_targets or lookahead_targets)
+    if lookahead_targets:
+        learner = LookaheadTargetLearner(env, net, alpha=alpha, plies=window, every=every, epsilon=epsilon, seed=seed)
+        steps, per = -(-plies // window), window
+    elif playout_targets:
         learner = PlayoutTargetLearner(env, net, alpha=alpha, plies=window, trials=playout_targets, every=every,
                                        max_plies=max_plies, leaf=leaf, epsilon=epsilon, seed=seed)
         steps, per = -(-plies // window), window
@@ -62,7 +75,7 @@ def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rul
     period = max(1, steps // max(1, report))
     err = torch.zeros((), device=env.device)
     for step in range(steps):
-        if playout_targets:  # the root-mean-square error against the playout targets
+        if fitted:  # the root-mean-square error against the playout (two-ply) targets
             loss = learner.step()[0]
             err += (loss[0] / loss[1].clamp(min=1.0)).sqrt().float()
         else:
@@ -70,7 +83,7 @@ def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rul
         if (step + 1) % period == 0 or step + 1 == steps:
             n = (step % period) + 1
             ep = int(env.stats().sum(0)[0])
-            what = "rms error" if playout_targets else "mean |delta|"
+            what = "rms error" if fitted else "mean |delta|"
             print(f"ply {(step + 1) * per}: {what} {float(err) / n:.4f}, {ep} games finished")
             err.zero_()
     torch.save(net.state_dict(), out)
@@ -97,6 +110,9 @@ if __name__ == "__main__":
     ap.add_argument("--every", type=int, default=1, help="playout roots: the positions of every S-th ply of a window")
     ap.add_argument("--max-plies", type=int, default=400, help="a playout trial's length bound")
     ap.add_argument("--leaf", action="store_true", help="count an unfinished trial at the net's value where it stopped")
+    ap.add_argument("--lookahead-targets", action="store_true",
+                    help="(with --window K): fit the net onto the two-ply values of each window's positions")
     a = ap.parse_args()
     main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out, window=a.window,
-         playout_targets=a.playout_targets, every=a.every, max_plies=a.max_plies, leaf=a.leaf)
+         playout_targets=a.playout_targets, every=a.every, max_plies=a.max_plies, leaf=a.leaf,
+         lookahead_targets=a.lookahead_targets)

@@ -84,4 +84,13 @@ inline int check_value_mlp(const narde_value_mlp* net, int perspective, float* v
   return NARDE_OK;
 }
 
+// The calls over n given public records (u32[n][8]; narde_records_lookahead,
+// narde_turn_records_lookahead): a record a workgroup, so n is a grid's x.
+inline int check_given_records(int64_t n, const void* records) {
+  if (!records) return fail(NARDE_EINVAL, "NULL argument");
+  if (n < 1 || n >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "n %lld outside 1 .. 2^31 - 1", (long long)n);
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  return NARDE_OK;
+}
+
 }  // namespace narde_host

@@ -57,7 +57,11 @@ __device__ __forceinline__ float look_better(float x, float y, bool smallest) {
 // launched over cap rows: a wave whose row is at or past min(offsets[n], cap)
 // leaves, and so does a terminal row's (its value is the fill's)
 // (a row per workgroup of kWaves waves: every exit before the barrier is the whole workgroup's)
-template <int kWaves>
+// kGiven (narde_records_lookahead): the rows are the
+// caller's n public records -- rows = n, no offsets; word 7 is the ply counter
+// and is not looked at; a finished record (record_finished) gets NaN.  New
+// instantiations: the existing two are the ones they were.
+template <int kWaves, bool kGiven = false>
 __global__ void __launch_bounds__(64 * kWaves) k_aft_look(LookArgs a, ValNet vn) {
   __shared__ AftScan scan[kWaves];
   __shared__ ValStage stage[kWaves];
@@ -67,11 +71,20 @@ __global__ void __launch_bounds__(64 * kWaves) k_aft_look(LookArgs a, ValNet vn)
   ValStage& VS = stage[wave];
   const int lane = threadIdx.x & 63;
   const int64_t R = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
-  const int64_t rows = min((int64_t)a.offsets[a.n], a.cap);
+  int64_t rows;
+  if constexpr (kGiven) rows = a.n;
+  else rows = min((int64_t)a.offsets[a.n], a.cap);
   if (R >= rows) return;
   const uint4 ra = a.rec[2 * R];
   const uint4 rb = a.rec[2 * R + 1];
-  if (rb.w != 0u) return;  // the step's reward: a terminal row
+  if constexpr (kGiven) {
+    if (record_finished(rb.z)) {  // no two-ply value
+      if (threadIdx.x == 0) vn.value[R] = __builtin_nanf("");
+      return;
+    }
+  } else {
+    if (rb.w != 0u) return;  // the step's reward: a terminal row
+  }
   const Side s = side_from_record(ra, rb);
   const bool smallest = s.black != 0u;  // the values are white's: black replies with the smallest
   ValRoot vr;

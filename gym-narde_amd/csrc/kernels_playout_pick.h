@@ -159,4 +159,35 @@ __global__ void __launch_bounds__(kBlock) k_playout_pick(PlayoutPickArgs a, cons
   if (a.row) a.row[i] = (int32_t)r;
 }
 
+// ------------------------------------------------------------ the pick over given slot scores
+// narde_slot_pick / narde_turn_slot_pick: k_playout_pick
+// with the caller's score a slot in place of the playouts' sums
+// (slot_pick_slot); the same outputs.
+struct SlotPickArgs {
+  Planes pl;
+  int n, k;
+  const int32_t* __restrict__ sel;    // [n][k]
+  int64_t cap;
+  const float* __restrict__ value;    // [cap] x ld
+  int64_t ld;
+  const int8_t* __restrict__ reward;  // [cap]
+  const float* slot_score;            // [n][k]
+  int32_t* __restrict__ row;          // [n] or NULL
+  float* score;                       // [n][k] or NULL (may be slot_score itself)
+};
+
+template <typename W, int kNoRow>
+__global__ void __launch_bounds__(kBlock) k_slot_pick(SlotPickArgs a, const W* __restrict__ column,
+                                                      W* __restrict__ out) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const size_t s0 = (size_t)i * (size_t)a.k;
+  const bool smallest = ((a.pl.p1[i].z >> 10) & 1u) != 0u;
+  const int bi = slot_pick_slot(a.sel + s0, a.k, a.cap, a.value, a.ld, a.reward, a.slot_score + s0, smallest,
+                                a.score ? a.score + s0 : nullptr);
+  const int64_t r = bi >= 0 ? (int64_t)a.sel[s0 + bi] : -1;
+  out[i] = r >= 0 ? column[r] : static_cast<W>(kNoRow);
+  if (a.row) a.row[i] = (int32_t)r;
+}
+
 }  // namespace

@@ -165,7 +165,18 @@ __device__ __forceinline__ bool turn_look_roll(TurnLook& lk, int d0, int d1, uin
 // min(offsets[n], cap) leaves, and so does a terminal row's (its value is the
 // fill's, its redo word 0)
 // (a row per workgroup of kWaves waves: every exit before the barrier is the whole workgroup's)
-template <int kWaves>
+// kGiven (narde_turn_records_lookahead), here and in the
+// two passes below: the rows are the n pieces k_turn_look_pack made of the
+// caller's records -- rows = n, no offsets; a finished record's piece has word
+// 7 set, as a terminal row's.  New instantiations: the existing ones are the
+// ones they were.
+template <bool kGiven>
+__device__ __forceinline__ int64_t turn_look_rows(const TurnLookArgs& a) {
+  if constexpr (kGiven) return (int64_t)a.n;
+  else return min((int64_t)a.offsets[a.n], a.cap);
+}
+
+template <int kWaves, bool kGiven = false>
 __global__ void __launch_bounds__(64 * kWaves) k_turn_look(TurnLookArgs a, ValNet vn) {
   __shared__ TurnFrontLds front[kWaves];
   __shared__ TurnScan scan[kWaves];
@@ -177,7 +188,7 @@ __global__ void __launch_bounds__(64 * kWaves) k_turn_look(TurnLookArgs a, ValNe
   ValStage& VS = stage[wave];
   const int lane = threadIdx.x & 63;
   const int64_t R = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
-  const int64_t rows = min((int64_t)a.offsets[a.n], a.cap);
+  const int64_t rows = turn_look_rows<kGiven>(a);
   if (R >= rows) return;
   uint32_t* const row = a.row + R * kTurnLookRowWords;
   const uint4 ra = reinterpret_cast<const uint4*>(row)[0];
@@ -221,6 +232,7 @@ __global__ void __launch_bounds__(64 * kWaves) k_turn_look(TurnLookArgs a, ValNe
 // -- one env's -- go to different waves); a marked row's root forward runs
 // once, then each marked roll's walk with kTurnFrontBig nodes a level in LDS
 // and, if that is outgrown too, in the wave's piece of the slab.
+template <bool kGiven = false>
 __global__ void __launch_bounds__(64) k_turn_look_overflow(TurnLookArgs a, ValNet vn) {
   __shared__ TurnScan scan;
   __shared__ ValStage stage;
@@ -230,7 +242,7 @@ __global__ void __launch_bounds__(64) k_turn_look_overflow(TurnLookArgs a, ValNe
   uint32_t* const pathA = reinterpret_cast<uint32_t*>(key + kTurnSlabKeys);
   uint32_t* const pathB = pathA + kTurnAftMax;
   const int lane = threadIdx.x & 63;
-  const int64_t rows = min((int64_t)a.offsets[a.n], a.cap);
+  const int64_t rows = turn_look_rows<kGiven>(a);
   const int64_t waves = (int64_t)gridDim.x;
   for (int64_t i0 = 0; (i0 * waves + (int64_t)blockIdx.x) < rows; i0 += 64) {
     const int64_t Rl = (i0 + lane) * waves + (int64_t)blockIdx.x;
@@ -272,12 +284,13 @@ __global__ void __launch_bounds__(64) k_turn_look_overflow(TurnLookArgs a, ValNe
 
 // value[R] = sum w m / sum w over the dice mode's unordered rolls a <= b, a
 // outer, b inner, w = 1 for a double and 2 otherwise; in double, rounded once
+template <bool kGiven = false>
 __global__ void __launch_bounds__(kTurnLookMeanBlock) k_turn_look_mean(TurnLookArgs a, float* __restrict__ value) {
   const int64_t R = (int64_t)blockIdx.x * kTurnLookMeanBlock + threadIdx.x;
-  const int64_t rows = min((int64_t)a.offsets[a.n], a.cap);
+  const int64_t rows = turn_look_rows<kGiven>(a);
   if (R >= rows) return;
   const uint32_t* const row = a.row + R * kTurnLookRowWords;
-  if (row[7] != 0u) return;  // a terminal row: the fill's outcome stands
+  if (row[7] != 0u) return;  // a terminal row: the fill's outcome stands (kGiven: the pack's NaN)
   const float* const best = reinterpret_cast<const float*>(row) + kTurnLookBest;
   double sum = 0.0, weight = 0.0;
   int k = 0;
@@ -290,6 +303,28 @@ __global__ void __launch_bounds__(kTurnLookMeanBlock) k_turn_look_mean(TurnLookA
     }
   }
   value[R] = (float)(sum / weight);
+}
+
+// narde_turn_records_lookahead's first pass, a lane per record: the caller's
+// public record into its 128-B row piece, as the record fills leave one -- word
+// 7 (the caller's ply counter, which no pass may read as a reward) replaced by
+// the mark of a finished record (record_finished), whose value is NaN here and
+// which the passes above then leave alone as a terminal row; the redo word
+// cleared.  The caller's records are only read.
+__global__ void __launch_bounds__(kTurnLookMeanBlock) k_turn_look_pack(const uint4* __restrict__ records, int64_t n,
+                                                                       uint32_t* __restrict__ row,
+                                                                       float* __restrict__ value) {
+  const int64_t R = (int64_t)blockIdx.x * kTurnLookMeanBlock + threadIdx.x;
+  if (R >= n) return;
+  const uint4 ra = records[2 * R];
+  uint4 rb = records[2 * R + 1];
+  const bool done = record_finished(rb.z);
+  rb.w = done ? 1u : 0u;
+  uint32_t* const piece = row + R * kTurnLookRowWords;
+  reinterpret_cast<uint4*>(piece)[0] = ra;
+  reinterpret_cast<uint4*>(piece)[1] = rb;
+  piece[kTurnLookRedo] = 0u;
+  if (done) value[R] = __builtin_nanf("");
 }
 
 }  // namespace

@@ -32,7 +32,9 @@
 //   kernels_turn_lookahead.h  FULL4 two-ply lookahead: the record fills, the
 //                       reply walk per (row, roll), its overflow pass and the
 //                       mean (k_turn_fill_rec, k_turn_look, k_turn_look_overflow,
-//                       k_turn_look_mean)
+//                       k_turn_look_mean); the look passes of both rule sets
+//                       have a second instantiation over a caller's records
+//                       (behind k_turn_look_pack here)
 //   kernels_turn_value_rollout.h  FULL4 value-greedy games in one launch: the
 //                       picking consumer of the level walk inside a ply loop
 //                       (k_turn_value_rollout)
@@ -46,7 +48,8 @@
 //                       rows' records as an output, an env's top-K rows as
 //                       playout roots, the pick over the playouts' sums
 //                       (k_aft_fill_records, k_turn_fill_records,
-//                       k_rows_topk, k_playout_pick)
+//                       k_rows_topk, k_playout_pick), the pick over given
+//                       slot scores (k_slot_pick)
 //   kernels_td.h        TD(lambda) on the value MLP: the trace pass, the TD
 //                       errors, the slab sums and the weight update
 //   kernels_td_window.h  windowed TD(lambda): the window's values, returns and
@@ -272,13 +275,9 @@ int expand_plays(narde_env* e, const AftArgs& a, const ValNet* vn, hipStream_t s
   return check_launch("k_aft_fill");
 }
 
-// FULL4's: the handle's workspace on its first call, the count passes, the
-// scan, the fills (scored with vn; with tr the record fills of the lookahead,
-// whose own passes the caller launches behind them; with pub the records fills
-// of narde_turn_afterstates_records, scored if vn is given)
-int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env, int8_t* play,
-                 float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st,
-                 const TurnRec* tr = nullptr, const TurnRec* pub = nullptr) {
+// The handle's FULL4 workspace, made by the first call that needs it (the
+// expansions below; narde_turn_records_lookahead, for the slab)
+int turn_workspace(narde_env* e, hipStream_t st) {
   if (!e->turn_slab) {
     // the workspace belongs to the handle and is made once, outside capture
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -295,6 +294,17 @@ int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offset
       return fail(NARDE_ENOMEM, "turn afterstate workspace: %s", hipGetErrorString(err));
     }
   }
+  return NARDE_OK;
+}
+
+// FULL4's: the handle's workspace on its first call, the count passes, the
+// scan, the fills (scored with vn; with tr the record fills of the lookahead,
+// whose own passes the caller launches behind them; with pub the records fills
+// of narde_turn_afterstates_records, scored if vn is given)
+int expand_turns(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env, int8_t* play,
+                 float* feat, int32_t* obs, int8_t* reward, const ValNet* vn, hipStream_t st,
+                 const TurnRec* tr = nullptr, const TurnRec* pub = nullptr) {
+  if (const int rc = turn_workspace(e, st)) return rc;
   TurnArgs a{e->pl, (int)e->n, rng_of(e), dice, cap, offsets, row_env, play, feat, obs, reward, e->turn_ovf,
              e->turn_slab};
   const int cw = kTurnCountBlock / 64, fw = kTurnFillBlock / 64;
@@ -390,6 +400,35 @@ int playout_pick_rows(narde_env* e, int k, const int32_t* sel, int64_t cap, cons
   k_playout_pick<W, kNoRow><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(a, static_cast<const W*>(column),
                                                                             static_cast<W*>(out));
   return check_launch("k_playout_pick");
+}
+
+// narde_slot_pick's and narde_turn_slot_pick's: the same with the caller's
+// slot scores in place of the trials and sums
+template <typename W, int kNoRow>
+int slot_pick_rows(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value, int64_t ld_value,
+                   const int8_t* reward, const void* column, const float* slot_score, void* out, int32_t* row,
+                   float* score, void* stream, const char* misaligned) {
+  if (!e || !sel || !value || !reward || !slot_score || !column || !out) return fail(NARDE_EINVAL, "NULL argument");
+  if (k < 1 || k > NARDE_TOPK_MAX) return fail(NARDE_EINVAL, "k %d outside 1 .. NARDE_TOPK_MAX = %d", k, NARDE_TOPK_MAX);
+  if (cap < 0) return fail(NARDE_EINVAL, "cap %lld is negative", (long long)cap);
+  if (ld_value < 1) return fail(NARDE_EINVAL, "bad value stride");
+  if (e->n * (int64_t)k >= (int64_t(1) << 31)) return fail(NARDE_EINVAL, "B x k must stay below 2^31 (k %d)", k);
+  if ((reinterpret_cast<uintptr_t>(column) % sizeof(W)) || (reinterpret_cast<uintptr_t>(out) % sizeof(W)))
+    return fail(NARDE_EINVAL, "%s", misaligned);
+  DeviceGuard dg(e->device);
+  const SlotPickArgs a{e->pl, (int)e->n, k, sel, cap, value, ld_value, reward, slot_score, row, score};
+  k_slot_pick<W, kNoRow><<<grid(e->n), kBlock, 0, (hipStream_t)stream>>>(a, static_cast<const W*>(column),
+                                                                         static_cast<W*>(out));
+  return check_launch("k_slot_pick");
+}
+
+// narde_records_lookahead's and narde_turn_records_lookahead's checks of the
+// handle, the records, the net and the values, and the kernels' view of the net
+int check_records_lookahead(const narde_env* e, int64_t n, const void* records, const narde_value_mlp* net,
+                            float* value, ValNet& vn) {
+  if (!e || !net || !value) return fail(NARDE_EINVAL, "NULL argument");
+  if (const int rc = check_given_records(n, records)) return rc;
+  return check_value_net(net, 1, value, vn);
 }
 
 }  // namespace
@@ -843,6 +882,21 @@ int narde_afterstates_lookahead(narde_env* e, const uint8_t* dice, int64_t cap, 
   return check_launch("k_aft_look");
 }
 
+int narde_records_lookahead(narde_env* e, int64_t n, const void* records, const narde_value_mlp* net, float* value,
+                            void* stream) {
+  ValNet vn;
+  if (const int rc = check_records_lookahead(e, n, records, net, value, vn)) return rc;
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  // the look kernel reads the caller's records: rows = n, no offsets
+  const LookArgs la{(const uint4*)records, nullptr, (int)n, n, e->dice_mode};
+  if (n <= kLookSplitRows)  // a short launch, as narde_afterstates_lookahead's (the same bits)
+    k_aft_look<kLookSplit, true><<<(unsigned)n, 64 * kLookSplit, 0, st>>>(la, vn);
+  else
+    k_aft_look<1, true><<<(unsigned)n, 64, 0, st>>>(la, vn);
+  return check_launch("k_aft_look<given>");
+}
+
 int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* codes, int64_t cap,
                           const float* value, int64_t ld_value, int perspective, const float* epsilon,
                           uint64_t seed, const int64_t* tag, int16_t* actions, int32_t* row, void* stream) {
@@ -1109,11 +1163,39 @@ int narde_turn_afterstates_lookahead(narde_env* e, const uint8_t* dice, int64_t 
   else
     k_turn_look<1><<<(unsigned)rows, 64, 0, st>>>(la, vn);
   if (const int rc = check_launch("k_turn_look")) return rc;
-  k_turn_look_overflow<<<kTurnOvfWaves, 64, 0, st>>>(la, vn);
+  k_turn_look_overflow<false><<<kTurnOvfWaves, 64, 0, st>>>(la, vn);
   if (const int rc = check_launch("k_turn_look_overflow")) return rc;
-  k_turn_look_mean<<<(unsigned)((rows + kTurnLookMeanBlock - 1) / kTurnLookMeanBlock), kTurnLookMeanBlock, 0, st>>>(
-      la, value);
+  k_turn_look_mean<false>
+      <<<(unsigned)((rows + kTurnLookMeanBlock - 1) / kTurnLookMeanBlock), kTurnLookMeanBlock, 0, st>>>(la, value);
   return check_launch("k_turn_look_mean");
+}
+
+int narde_turn_records_lookahead(narde_env* e, int64_t n, const void* records, const narde_value_mlp* net,
+                                 float* value, void* scratch, int64_t scratch_bytes, void* stream) {
+  ValNet vn;
+  if (const int rc = check_records_lookahead(e, n, records, net, value, vn)) return rc;
+  if (!scratch) return fail(NARDE_EINVAL, "NULL argument");
+  if (scratch_bytes < 0 || scratch_bytes / (4 * kTurnLookRowWords) < n)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES = 128 x n %lld",
+                (long long)scratch_bytes, (long long)n);
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  hipStream_t st = (hipStream_t)stream;
+  if (const int rc = turn_workspace(e, st)) return rc;  // the overflow pass's slab
+  const unsigned lanes = (unsigned)((n + kTurnLookMeanBlock - 1) / kTurnLookMeanBlock);
+  k_turn_look_pack<<<lanes, kTurnLookMeanBlock, 0, st>>>((const uint4*)records, n, (uint32_t*)scratch, value);
+  if (const int rc = check_launch("k_turn_look_pack")) return rc;
+  // the passes of narde_turn_afterstates_lookahead over the n pieces: rows = n, no offsets
+  const TurnLookArgs la{(uint32_t*)scratch, nullptr, (int)n, n, e->dice_mode, e->turn_slab};
+  if (n <= kTurnLookSplitRows)
+    k_turn_look<kTurnLookSplit, true><<<(unsigned)n, 64 * kTurnLookSplit, 0, st>>>(la, vn);
+  else
+    k_turn_look<1, true><<<(unsigned)n, 64, 0, st>>>(la, vn);
+  if (const int rc = check_launch("k_turn_look<given>")) return rc;
+  k_turn_look_overflow<true><<<kTurnOvfWaves, 64, 0, st>>>(la, vn);
+  if (const int rc = check_launch("k_turn_look_overflow<given>")) return rc;
+  k_turn_look_mean<true><<<lanes, kTurnLookMeanBlock, 0, st>>>(la, value);
+  return check_launch("k_turn_look_mean<given>");
 }
 
 int narde_afterstates_records(narde_env* e, const uint8_t* dice, int64_t cap, int32_t* offsets, int32_t* row_env,
@@ -1180,6 +1262,20 @@ int narde_turn_playout_pick(narde_env* e, int k, const int32_t* sel, int64_t cap
                             void* stream) {
   return playout_pick_rows<uint64_t, -1>(e, k, sel, cap, value, ld_value, reward, play, trials, sums, leaf, out_play,
                                          row, score, stream, "play and out_play must be 8-B aligned");
+}
+
+int narde_slot_pick(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value, int64_t ld_value,
+                    const int8_t* reward, const int16_t* codes, const float* slot_score, int16_t* actions,
+                    int32_t* row, float* score, void* stream) {
+  return slot_pick_rows<uint32_t, 0>(e, k, sel, cap, value, ld_value, reward, codes, slot_score, actions, row, score,
+                                     stream, "codes and actions must be 4-B aligned");
+}
+
+int narde_turn_slot_pick(narde_env* e, int k, const int32_t* sel, int64_t cap, const float* value, int64_t ld_value,
+                         const int8_t* reward, const int8_t* play, const float* slot_score, int8_t* out_play,
+                         int32_t* row, float* score, void* stream) {
+  return slot_pick_rows<uint64_t, -1>(e, k, sel, cap, value, ld_value, reward, play, slot_score, out_play, row, score,
+                                      stream, "play and out_play must be 8-B aligned");
 }
 
 int narde_value_td_trace(narde_env* e, const narde_value_mlp_train* net, float decay, float* trace, int64_t ld_trace,

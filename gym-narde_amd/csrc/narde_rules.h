@@ -2821,6 +2821,34 @@ NARDE_FN int playout_pick_slot(const int32_t* sel, int k, int64_t cap, const flo
   return bi;
 }
 
+// ------------------------------------------------- two-ply values of given records
+// A public record whose game is over -- either side has its 15 checkers off:
+// a finished game, or the none record -- from its word 6.  Such a record has no
+// two-ply value (NaN).  Word 7, the ply counter, and elapsed say nothing here.
+NARDE_FN bool record_finished(uint32_t misc) { return (misc & 15u) == 15u || ((misc >> 4) & 15u) == 15u; }
+
+// playout_pick_slot over given scores: slot s of a candidate (sel[s] in
+// 0 .. cap - 1) scores value[r ld] where reward[r] != 0 -- a terminal row's
+// known outcome -- and slot_score[s] otherwise; no candidate scores NaN and is
+// never offered.  The same order: the largest when white moves, the smallest
+// when black does, the lowest slot on ties, NaN as argmax_takes takes it.
+NARDE_FN int slot_pick_slot(const int32_t* sel, int k, int64_t cap, const float* value, int64_t ld,
+                            const int8_t* reward, const float* slot_score, bool smallest, float* score) {
+  float best = 0.0f;
+  int bi = -1;
+  for (int s = 0; s < k; ++s) {
+    const int64_t r = sel[s];
+    float sc = __builtin_nanf("");
+    if (r >= 0 && r < cap) {
+      sc = reward[r] != 0 ? value[r * ld] : slot_score[s];
+      const float x = smallest ? -sc : sc;
+      if (argmax_takes(x, s, best, bi)) { best = x; bi = s; }
+    }
+    if (score) score[s] = sc;
+  }
+  return bi;
+}
+
 // ------------------------------------------- the value MLP's supervised fit
 // narde_value_fit's and narde_playout_targets' arithmetic (kernels_value_fit.h;
 // the host check tests/hostcheck/hostcheck_value_fit.cpp runs the same

@@ -156,6 +156,10 @@ SIGNATURES = {
     "narde_rows_topk": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "narde_playout_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_turn_playout_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_records_lookahead": (_i32, [_vp, _i64, _vp, ctypes.POINTER(ValueMlp), _vp, _vp]),
+    "narde_turn_records_lookahead": (_i32, [_vp, _i64, _vp, ctypes.POINTER(ValueMlp), _vp, _vp, _i64, _vp]),
+    "narde_slot_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_turn_slot_pick": (_i32, [_vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "narde_value_td_trace": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
     "narde_value_td_apply": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                     ctypes.c_float, ctypes.c_float, _i32, _vp, _i64, _vp, _vp]),

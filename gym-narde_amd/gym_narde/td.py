@@ -32,7 +32,9 @@ means, lookahead values, anything a caller can compute for a position --,
     theta <- theta + alpha sum_i w_i (target_i - v(s_i)) grad_theta v(s_i).
 PlayoutTargetLearner closes the loop with it: a window of self-play, Monte-Carlo
 playouts of the window's positions (VecNardeEnv.playout), their means as the
-targets (VecNardeEnv.playout_targets), one fit.
+targets (VecNardeEnv.playout_targets), one fit.  LookaheadTargetLearner
+ is the same loop with the two-ply values of the window's
+positions (VecNardeEnv.lookahead_records) as the targets.
 """
 import ctypes
 
@@ -280,6 +282,89 @@ class PlayoutTargetLearner:
         if self.result is not None:
             own += [x for x in (self.result.sums, self.result.outcome, self.result.length, self.result.leaf)
                     if x is not None]
+        if self._roll_scratch is not None:
+            own.append(self._roll_scratch)
+        return sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
+
+
+class LookaheadTargetLearner:
+    """Self-play and a fit onto the two-ply values of its positions (DESIGN.md
+    section 25): PlayoutTargetLearner with VecNardeEnv.lookahead_records() in
+    place of the playouts.  env: a VecNardeEnv (either rule set) with
+    autoreset; net: a ValueMLP on its device.  Every step: play() -- `plies`
+    plies of value-greedy self-play in one launch that records each ply's
+    position; targets() -- the positions of plies k % every == 0, N =
+    ceil(plies / every) * B roots, each root's target its two-ply value under
+    the net (the expectation, over its mover's rolls, of the mover's best
+    afterstate), its weight 1 -- 0 where that value is NaN (a finished
+    position); update() -- one narde_value_fit of those roots at step size
+    alpha (a sum over the roots).  epsilon: the explore probability of the
+    self-play (None: greedy).  Nothing is drawn besides the self-play: the same
+    arguments and the same number of steps give the same weight bits."""
+
+    def __init__(self, env, net, alpha, plies, every=1, epsilon=None, seed=0):
+        t = env.torch
+        _check_learner("LookaheadTargetLearner", env, net, 0.0)
+        if int(plies) < 1 or int(every) < 1:
+            raise ValueError("plies and every must be >= 1")
+        self.env, self.net, self.plies, self.every = env, net, int(plies), int(every)
+        self.alpha, self.seed = float(alpha), int(seed)
+        self.windows = 0
+        z = dict(device=env.device)
+        B, M = env.num_envs, -(-self.plies // self.every)
+        N = M * B
+        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
+        self.bufs = make(self.plies, records=True)
+        self.roots = t.zeros((N, 8), dtype=t.int32, **z)
+        self.target = t.zeros(N, dtype=t.float32, **z)
+        self.weight = t.zeros(N, dtype=t.float32, **z)
+        self.fitter = ValueFitter(env, net, N)
+        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
+        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
+        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
+
+    def play(self):
+        """The window's plies in one launch, the net on both sides; the
+        explore tag advances by them.  Returns the launch's buffers."""
+        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
+        if env.full:
+            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
+        else:
+            env.value_rollout(self.plies, self.net, **kw)
+        if self._tag is not None:
+            self._tag += self.plies
+        self.windows += 1
+        return self.bufs
+
+    def targets(self):
+        """The two-ply values of the window's positions.  Returns (target,
+        weight), each (N,), root j * B + e = env e before ply j * every (the
+        learner's own buffers); target NaN, weight 0, for a finished root."""
+        env, B, t = self.env, self.env.num_envs, self.env.torch
+        self.roots.view(-1, B, 8).copy_(self.bufs["records"][::self.every])
+        env.lookahead_records(self.roots, self.net, out=self.target)
+        self.weight.copy_(~t.isnan(self.target))
+        return self.target, self.weight
+
+    def update(self):
+        """One fit of the roots onto targets()' numbers.  Returns the loss
+        (2,) float64 = (sum w e^2, sum w) under the weights it found."""
+        return self.fitter.step(self.roots, self.target, self.weight, alpha=self.alpha)
+
+    def step(self):
+        """play(), targets(), update().  Returns (loss, target, weight)."""
+        self.play()
+        self.targets()
+        return self.update(), self.target, self.weight
+
+    def values(self):
+        """v (N,) of the last update, under the weights it found."""
+        return self.fitter.values()
+
+    def memory_bytes(self):
+        """Device memory the learner owns (the env keeps lookahead_records()'
+        scratch of a rules="full4" env)."""
+        own = [x for x in self.bufs.values() if x is not None] + [self.roots, self.target, self.weight]
         if self._roll_scratch is not None:
             own.append(self._roll_scratch)
         return sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()

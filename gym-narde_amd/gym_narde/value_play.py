@@ -14,7 +14,9 @@ With a value_net.ValueMLP the rows are scored inside the expansion
 (lookahead_afterstates(): each row's value is the expectation, over the
 opponent's rolls, of the opponent's best reply under the same net);
 LookaheadPlayer is that search for either rule set
-(lookahead_turn_afterstates() on a rules="full4" env).
+(lookahead_turn_afterstates() on a rules="full4" env); with top=k it searches
+only each env's k best rows by one-ply value (top_rows(),
+VecNardeEnv.lookahead_records(), pick_slots()).
 play_match() answers "is net A better than net B, or than random play?":
 whole games in one launch a colour assignment (VecNardeEnv.value_rollout());
 play_turn_match() is the same on a rules="full4" env
@@ -109,14 +111,46 @@ class LookaheadPlayer(ValuePlayer):
     over the opponent's rolls, of the opponent's best reply under net (a
     value_net.ValueMLP) -- lookahead_afterstates() on a rules="ref2" env,
     lookahead_turn_afterstates() on a rules="full4" one.  The fused path,
-    perspective "white"; cap and step() as ValuePlayer's."""
+    perspective "white"; cap and step() as ValuePlayer's.
+    top: None -- every row is searched.  top = k (1 .. NARDE_TOPK_MAX) -- the
+    pruned search: only each env's k best rows by
+    one-ply value are searched, and the best of those by two-ply value is
+    played.  Five device calls a ply with static shapes: recorded_afterstates()
+    / recorded_turn_afterstates(), top_rows(k, records), lookahead_records()
+    of the roots, pick_slots(), step().  step() then returns the same tuple --
+    values the rows' one-ply values -- with sel and score (the slots' two-ply
+    scores) in info.  top = 1 plays exactly ValuePlayer's moves."""
 
-    def __init__(self, env, net, cap=None):
+    def __init__(self, env, net, cap=None, top=None):
+        from . import _lib
+
         if not (hasattr(net, "struct") and hasattr(net, "pack")):
             raise TypeError("LookaheadPlayer needs a gym_narde.value_net.ValueMLP")
         super().__init__(env, net, perspective="white", fused=True, cap=cap, plies=1)
         self.plies = 2
         self._lookahead = env.lookahead_turn_afterstates if env.full else env.lookahead_afterstates
+        if top is not None:
+            if isinstance(top, bool) or not isinstance(top, int):
+                raise TypeError("top must be None or an int")
+            if not 1 <= top <= _lib.TOPK_MAX:
+                raise ValueError(f"top must be in 1 .. {_lib.TOPK_MAX}")
+        self.top = top
+        self._recorded = env.recorded_turn_afterstates if env.full else env.recorded_afterstates
+
+    def step(self, epsilon=None, tag=None, seed=0):
+        if self.top is None:
+            return super().step(epsilon, tag, seed)
+        if epsilon is not None or tag is not None:
+            raise ValueError("the pruned search (top) plays greedily: no epsilon")
+        env = self.env
+        dice = env.dice()
+        aft, values, records = self._recorded(self.net, dice, cap=self.cap)
+        sel, roots = env.top_rows(aft, values, self.top, records)
+        two = env.lookahead_records(roots, self.net)
+        actions, row, score = env.pick_slots(aft, values, sel, two.view(env.num_envs, self.top))
+        obs, reward, terminated, truncated, info = env.step(actions)
+        info = dict(info, dice=dice, row=row, sel=sel, score=score)
+        return obs, reward, terminated, truncated, info, aft, values, actions
 
 
 class PlayoutPlayer:

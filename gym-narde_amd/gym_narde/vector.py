@@ -724,6 +724,97 @@ class VecNardeEnv:
         self._keep = (v, sel, sums, lf)
         return actions, row, score
 
+    def lookahead_records(self, records, net, out=None):
+        """White's two-ply value of given positions (narde_records_lookahead /
+        narde_turn_records_lookahead by the env's rules):
+        what lookahead_afterstates() / lookahead_turn_afterstates() give a row,
+        for any records -- top_rows()' roots, a records rollout's
+        bufs["records"], state_records().  records: an (n, 8) int32 device
+        tensor; its ply-counter word and elapsed are ignored.  Returns an (n,)
+        float32 tensor: the mean, over the rolls of the record's mover in the
+        env's dice mode, of the mover's best afterstate under net (the
+        smallest one-ply value for black, the largest for white; terminal
+        replies at their outcome); NaN for a record whose game is over (either
+        side has 15 off: a finished game, top_rows()' none record).  On the
+        records of a roll's rows the values are the full searches' bit for
+        bit.  This env's positions, ply counter and statistics are neither
+        read nor written.  out: an (n,) float32 tensor to write into.
+        rules="full4": the call's 128-byte row pieces live in a scratch tensor
+        kept on the env and grown when a later call has more records -- a
+        caller capturing a graph makes its first call outside capture, with its
+        largest n.  No synchronise."""
+        t = self.torch
+        if (not isinstance(records, t.Tensor) or records.dtype != t.int32 or records.device != self.device
+                or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8 or records.shape[0] < 1):
+            raise ValueError("records must be a contiguous (n, 8) int32 device tensor of records, n >= 1")
+        if not hasattr(net, "struct"):
+            raise TypeError("net must be a gym_narde.value_net.ValueMLP")
+        mlp = net.struct()
+        if net.l1.weight.device != self.device:
+            raise ValueError("the net must live on the env's device")
+        n = int(records.shape[0])
+        if out is None:
+            out = t.empty(n, dtype=t.float32, device=self.device)
+        elif (tuple(out.shape) != (n,) or out.dtype != t.float32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous (n,) float32 device tensor")
+        scratch = None
+        if self.full:
+            need = _lib.turn_lookahead_scratch_bytes(n)
+            if getattr(self, "_records_look_scratch", None) is None or self._records_look_scratch.numel() < need:
+                self._records_look_scratch = t.empty(need, dtype=t.uint8, device=self.device)
+            scratch = self._records_look_scratch
+            self.handle.call("narde_turn_records_lookahead", n, _lib.ptr(records), ctypes.byref(mlp), _lib.ptr(out),
+                             _lib.ptr(scratch), int(scratch.numel()), self._s())
+        else:
+            self.handle.call("narde_records_lookahead", n, _lib.ptr(records), ctypes.byref(mlp), _lib.ptr(out),
+                             self._s())
+        self._keep = (records, net, mlp, out, scratch)
+        return out
+
+    def pick_slots(self, aft, values, sel, slot_score, out=None):
+        """The move by given scores of top_rows()' candidates (narde_slot_pick /
+        narde_turn_slot_pick by the env's rules):
+        pick_playout() with slot_score (B, k) float32 -- white's score of each
+        slot, e.g. lookahead_records() of top_rows()' roots reshaped -- in
+        place of the playouts.  A slot's score: a terminal row's outcome
+        (values[row]); else slot_score; an empty slot's is NaN and never
+        picked.  The largest when white moves, the smallest when black does,
+        the lowest slot on ties, NaN as the picks take it.  Returns (actions
+        (B,2) int16 or play (B,4,2) int8 for step(), row (B,) int32, score
+        (B, k) float32); -1 and (0, 0) / an all -1 play for an env with no
+        candidate.  out: an earlier call's triple to write into.  Call it
+        before the step.  No synchronise."""
+        t, B = self.torch, self.num_envs
+        kind = _FULL4_ROWS if self.full else _REF2_ROWS
+        if (not isinstance(sel, t.Tensor) or sel.dim() != 2 or sel.shape[0] != B or sel.dtype != t.int32
+                or not sel.is_contiguous() or sel.device != self.device):
+            raise ValueError("sel must be top_rows()' (B, k) int32 tensor")
+        k = int(sel.shape[1])
+        if not 1 <= k <= _lib.TOPK_MAX:
+            raise ValueError(f"k must be in 1 .. {_lib.TOPK_MAX}")
+        if (not isinstance(slot_score, t.Tensor) or slot_score.dtype != t.float32 or slot_score.device != self.device
+                or not slot_score.is_contiguous() or slot_score.numel() != B * k
+                or tuple(slot_score.shape) not in ((B, k), (B * k,))):
+            raise ValueError("slot_score must be a contiguous (B, k) or (B * k,) float32 device tensor")
+        v = self._row_values(aft, values)
+        if out is not None:
+            actions, row, score = out
+        else:
+            actions = t.empty((B,) + kind.shape, dtype=getattr(t, kind.dtype), device=self.device)
+            row = t.empty(B, dtype=t.int32, device=self.device)
+            score = t.empty((B, k), dtype=t.float32, device=self.device)
+        if aft.cap == 0:  # no row anywhere (and no array to read)
+            actions.fill_(kind.no_row)
+            row.fill_(-1)
+            score.fill_(float("nan"))
+            return actions, row, score
+        self.handle.call("narde_turn_slot_pick" if self.full else "narde_slot_pick", k, _lib.ptr(sel), aft.cap,
+                         _lib.ptr(v), max(1, v.stride(0)), _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)),
+                         _lib.ptr(slot_score), _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score), self._s())
+        self._keep = (v, sel, slot_score)
+        return actions, row, score
+
     def _pick_rows(self, k, aft, values, perspective, epsilon, tag, seed):
         """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""
         if perspective not in PERSPECTIVES:

@@ -751,6 +751,70 @@ int narde_turn_playout_pick(narde_env *env, int k, const int32_t *sel, int64_t c
                             const int8_t *play, int trials, const int32_t *sums, const float *leaf,
                             int8_t *out_play, int32_t *row, float *score, void *stream);
 
+/* Two-ply values of given positions, and the pick over given slot scores
+ * (DESIGN.md section 25): what narde_afterstates_lookahead /
+ * narde_turn_afterstates_lookahead compute a row, for any records -- a
+ * narde_rows_topk's roots (pruned two-ply play), a rollout window's recorded
+ * positions (two-ply training targets), narde_state_records' positions.
+ *
+ * narde_records_lookahead (REF2), narde_turn_records_lookahead (FULL4):
+ * records u32[n][8], 16-B aligned, in the public record layout (what
+ * narde_state_records, the records rollouts, narde_*_afterstates_records and
+ * narde_rows_topk's roots write), are only read.  value[i] is WHITE's value of
+ * records[i] with its mover about to roll: exactly the per-row definition of
+ * the two calls above with s_r := records[i] -- REF2 the mean over the 36 (30
+ * under NARDE_DICE_NODOUBLES) ordered rolls of the mover's best
+ * narde_afterstates_scored value at perspective 1 (black the smallest, white
+ * the largest; terminal replies at their outcome; a roll with no reply what
+ * narde_step((0, 0)) leaves, the code-0 exception included); FULL4 the
+ * weighted mean over the 21 (15) unordered rolls of the best whole-turn
+ * reply, exact through both overflow tiers, a pass scoring the record with
+ * the mover flipped.  The summation order and the one rounding are those
+ * calls': on the records of a roll's rows the values are theirs bit for bit.
+ * Word 7 -- the ply counter, not a reward -- and elapsed are ignored.  A
+ * record in which either side has 15 checkers off (a finished game;
+ * narde_rows_topk's none record) gets value[i] = NaN.  Of the handle only the
+ * device, the dice mode and (FULL4) the overflow workspace are read; no env is
+ * touched.  The same bits on every call and for either launch shape (up to
+ * 3,072 records a record's rolls go over four waves, past that one wave a
+ * record).  Nothing at or past value[n] is written.
+ * scratch (FULL4): device memory, 16-B aligned, scratch_bytes >=
+ * NARDE_TURN_LOOKAHEAD_SCRATCH_BYTES(n): a pack pass copies each record into
+ * its 128-B row piece; its contents afterwards are unspecified.
+ * Stream-ordered, allocate nothing, no synchronise, graph-capturable -- FULL4
+ * once the handle's workspace exists (narde_turn_afterstates' rule: the
+ * handle's first FULL4 call, this one included, outside capture).
+ * NARDE_EINVAL before any device call: a NULL handle, records, net or value;
+ * n < 1 or n >= 2^31; records not 16-B aligned; the scored call's net cases;
+ * FULL4: a NULL, misaligned or too small scratch.
+ *
+ * narde_slot_pick / narde_turn_slot_pick: narde_playout_pick /
+ * narde_turn_playout_pick with a given score a slot in place of the playouts'
+ * sums.  slot_score f32[B][k]; a slot's score: sel < 0 -- NaN (no candidate,
+ * never picked); reward[r] != 0 -- value[r * ld_value], the known outcome;
+ * else slot_score[e][i].  The largest score when white moves (the env's
+ * record), the smallest when black does, the lowest slot on ties, NaN as the
+ * picks take it.  The outputs are that call's: actions / out_play ready for
+ * narde_step / narde_step_full, (0, 0) or the all -1 play and row -1 for an
+ * env with no candidate; optional row i32[B], score f32[B][k] (score may be
+ * slot_score itself).  NARDE_EINVAL: a NULL handle, sel, value, reward,
+ * slot_score, codes / play or actions / out_play; k outside 1 ..
+ * NARDE_TOPK_MAX; cap < 0; ld_value < 1; B * k >= 2^31; codes and actions not
+ * 4-B (play and out_play not 8-B) aligned. */
+int narde_records_lookahead(narde_env *env, int64_t n, const void *records,
+                            const narde_value_mlp *net, float *value, void *stream);
+int narde_turn_records_lookahead(narde_env *env, int64_t n, const void *records,
+                                 const narde_value_mlp *net, float *value, void *scratch,
+                                 int64_t scratch_bytes, void *stream);
+int narde_slot_pick(narde_env *env, int k, const int32_t *sel, int64_t cap, const float *value,
+                    int64_t ld_value, const int8_t *reward, const int16_t *codes,
+                    const float *slot_score, int16_t *actions, int32_t *row, float *score,
+                    void *stream);
+int narde_turn_slot_pick(narde_env *env, int k, const int32_t *sel, int64_t cap, const float *value,
+                         int64_t ld_value, const int8_t *reward, const int8_t *play,
+                         const float *slot_score, int8_t *out_play, int32_t *row, float *score,
+                         void *stream);
+
 /* TD(lambda) on that value MLP, trained in place on the device (DESIGN.md
  * section 16). narde_value_mlp_train: narde_value_mlp's fields, the weights
  * writable, and an optional mirror of the first layer: w1, row-major
