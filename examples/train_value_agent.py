@@ -27,10 +27,18 @@ positions (--every S as above) are valued two plies deep under the net itself
 -- the expectation, over the mover's rolls, of the mover's best afterstate --
 and the net is fitted onto those values.  The file written is the same.
 
+--optimizer sgd|adam, next to --window K (any of the three learners above),
+applies the update through gym_narde.td.ValueSGD / ValueAdam (DESIGN.md section
+26) instead of the plain call: the learner makes the summed gradient, the
+optimiser steps on it on the device -- --lr is Adam's step size (sgd uses
+--alpha), --clip C clips the gradient's norm to C first.  The file written is
+the same.
+
   python examples/train_value_agent.py [--envs B] [--plies N] [--hidden H] [--alpha A] [--lam L] [--epsilon E]
                                        [--rules ref2|full4] [--out-act none|sigmoid|tanh] [--seed S] [--out FILE]
                                        [--window K] [--playout-targets TRIALS [--every S] [--max-plies M] [--leaf]]
                                        [--lookahead-targets [--every S]]
+                                       [--optimizer sgd|adam [--lr LR] [--clip C]]
 
 Play the result:  python examples/play_value_agent.py --weights FILE --fused
 """
@@ -43,10 +51,11 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rules="ref2", out_act="tanh", seed=0,
          out="value_agent.pt", device="cuda", report=10, window=0, playout_targets=0, every=1, max_plies=400,
-         leaf=False, lookahead_targets=False):
+         leaf=False, lookahead_targets=False, optimizer=None, lr=1e-3, clip=None):
     import torch
 
-    from gym_narde.td import LookaheadTargetLearner, PlayoutTargetLearner, TDLambdaLearner, WindowTDLambdaLearner
+    from gym_narde.td import (LookaheadTargetLearner, PlayoutTargetLearner, TDLambdaLearner, ValueAdam, ValueSGD,
+                              WindowTDLambdaLearner)
     from gym_narde.value_net import ValueMLP
     from gym_narde.vector import VecNardeEnv
 
@@ -57,21 +66,36 @@ def main(envs=1024, plies=2000, hidden=80, alpha=1e-4, lam=0.7, epsilon=0.1, rul
         raise SystemExit("--playout-targets needs --window K (the plies a step plays and draws its roots from)")
     if lookahead_targets and (not window or playout_targets):
         raise SystemExit("--lookahead-targets needs --window K and excludes --playout-targets")
+    if (optimizer or clip is not None) and not window:
+        raise SystemExit("--optimizer and --clip need --window K (the online learner applies its update itself)")
+    opt = None
+    if optimizer == "adam":
+        opt = ValueAdam(net, lr, max_grad_norm=clip)
+    elif optimizer == "sgd" or clip is not None:
+        opt = ValueSGD(net, alpha, max_grad_norm=clip)
+    if opt is not None:
+        alpha = None  # the optimiser has the step size
     fitted = bool(playout_targets or lookahead_targets)
     if lookahead_targets:
-        learner = LookaheadTargetLearner(env, net, alpha=alpha, plies=window, every=every, epsilon=epsilon, seed=seed)
+        learner = LookaheadTargetLearner(env, net, alpha=alpha, plies=window, every=every, epsilon=epsilon, seed=seed,
+                                         optimizer=opt)
         steps, per = -(-plies // window), window
     elif playout_targets:
         learner = PlayoutTargetLearner(env, net, alpha=alpha, plies=window, trials=playout_targets, every=every,
-                                       max_plies=max_plies, leaf=leaf, epsilon=epsilon, seed=seed)
+                                       max_plies=max_plies, leaf=leaf, epsilon=epsilon, seed=seed, optimizer=opt)
         steps, per = -(-plies // window), window
     elif window:
-        learner = WindowTDLambdaLearner(env, net, alpha=alpha, lam=lam, plies=window, epsilon=epsilon, seed=seed)
+        learner = WindowTDLambdaLearner(env, net, alpha=alpha, lam=lam, plies=window, epsilon=epsilon, seed=seed,
+                                        optimizer=opt)
         steps, per = -(-plies // window), window
     else:
         learner = TDLambdaLearner(env, net, alpha=alpha, lam=lam, epsilon=epsilon, seed=seed)
         steps, per = plies, 1
     print(f"{envs} envs, hidden {hidden}, out {out_act}: learner memory {learner.memory_bytes() / 1e6:.1f} MB")
+    if opt is not None:
+        size = f"lr {lr:g}" if optimizer == "adam" else f"alpha {opt.alpha:g}"
+        print(f"optimizer {'adam' if optimizer == 'adam' else 'sgd'}: {size}, clip {clip}, "
+              f"{opt.memory_bytes() / 1e3:.1f} kB of state")
     period = max(1, steps // max(1, report))
     err = torch.zeros((), device=env.device)
     for step in range(steps):
@@ -112,7 +136,11 @@ if __name__ == "__main__":
     ap.add_argument("--leaf", action="store_true", help="count an unfinished trial at the net's value where it stopped")
     ap.add_argument("--lookahead-targets", action="store_true",
                     help="(with --window K): fit the net onto the two-ply values of each window's positions")
+    ap.add_argument("--optimizer", choices=("sgd", "adam"), default=None,
+                    help="(with --window K): step on the summed gradient with ValueSGD (--alpha) or ValueAdam (--lr)")
+    ap.add_argument("--lr", type=float, default=1e-3, help="ValueAdam's step size")
+    ap.add_argument("--clip", type=float, default=None, help="clip the gradient's norm to this before the step")
     a = ap.parse_args()
     main(a.envs, a.plies, a.hidden, a.alpha, a.lam, a.epsilon, a.rules, a.out_act, a.seed, a.out, window=a.window,
          playout_targets=a.playout_targets, every=a.every, max_plies=a.max_plies, leaf=a.leaf,
-         lookahead_targets=a.lookahead_targets)
+         lookahead_targets=a.lookahead_targets, optimizer=a.optimizer, lr=a.lr, clip=a.clip)

@@ -96,6 +96,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_td.h"
 #include "kernels_td_window.h"
 #include "kernels_value_fit.h"
+#include "kernels_value_optim.h"
 
 namespace {
 
@@ -1320,11 +1321,16 @@ int narde_value_td_apply(narde_env* e, const narde_value_mlp_train* net, float* 
   return check_launch("k_td_update");
 }
 
-int narde_value_td_window(narde_env* e, const narde_value_mlp_train* net, int plies, const void* records,
+// narde_value_td_window (the partial rows folded into the weights at step size
+// alpha) and narde_value_td_window_grad (folded into grad, no weight written)
+static int td_window_call(narde_env* e, const narde_value_mlp_train* net, int plies, const void* records,
                           const int32_t* reward, const uint8_t* terminated, const uint8_t* truncated, float alpha,
-                          float lam, float gamma, float* scratch, int64_t scratch_floats, float* delta, void* stream) {
+                          float lam, float gamma, float* scratch, int64_t scratch_floats, float* delta, bool to_grad,
+                          float* grad, void* stream) {
   if (!e || !net || !records || !reward || !terminated || !truncated || !scratch)
     return fail(NARDE_EINVAL, "NULL argument");
+  if (to_grad && !grad) return fail(NARDE_EINVAL, "NULL argument");
+  if (to_grad && !aligned16(grad)) return fail(NARDE_EINVAL, "grad must be 16-B aligned");
   if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
                                       net->out_act, kValLdMax))
     return rc;
@@ -1367,14 +1373,36 @@ int narde_value_td_window(narde_env* e, const narde_value_mlp_train* net, int pl
   k_tdw_grad<<<(unsigned)slabs, 2 * kTdBlock, (size_t)P * sizeof(float), st>>>((const uint4*)records, stored, tn, G, part,
                                                                            ld_part);
   if (const int rc = check_launch("k_tdw_grad")) return rc;
+  if (to_grad) {
+    k_td_fold<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>((int)P, part, ld_part, slabs, grad);
+    return check_launch("k_td_fold");
+  }
   k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
   return check_launch("k_td_update");
 }
 
-int narde_value_fit(int device, const narde_value_mlp_train* net, int64_t n, const void* records, const float* target,
-                    const float* weight, float alpha, float* scratch, int64_t scratch_floats, float* v, double* loss,
-                    void* stream) {
+int narde_value_td_window(narde_env* e, const narde_value_mlp_train* net, int plies, const void* records,
+                          const int32_t* reward, const uint8_t* terminated, const uint8_t* truncated, float alpha,
+                          float lam, float gamma, float* scratch, int64_t scratch_floats, float* delta, void* stream) {
+  return td_window_call(e, net, plies, records, reward, terminated, truncated, alpha, lam, gamma, scratch,
+                        scratch_floats, delta, false, nullptr, stream);
+}
+
+int narde_value_td_window_grad(narde_env* e, const narde_value_mlp_train* net, int plies, const void* records,
+                               const int32_t* reward, const uint8_t* terminated, const uint8_t* truncated, float lam,
+                               float gamma, float* scratch, int64_t scratch_floats, float* delta, float* grad,
+                               void* stream) {
+  return td_window_call(e, net, plies, records, reward, terminated, truncated, 0.0f, lam, gamma, scratch,
+                        scratch_floats, delta, true, grad, stream);
+}
+
+// narde_value_fit and narde_value_fit_grad, as td_window_call
+static int value_fit_call(int device, const narde_value_mlp_train* net, int64_t n, const void* records,
+                          const float* target, const float* weight, float alpha, float* scratch, int64_t scratch_floats,
+                          float* v, double* loss, bool to_grad, float* grad, void* stream) {
   if (!net || !records || !target || !scratch) return fail(NARDE_EINVAL, "NULL argument");
+  if (to_grad && !grad) return fail(NARDE_EINVAL, "NULL argument");
+  if (to_grad && !aligned16(grad)) return fail(NARDE_EINVAL, "grad must be 16-B aligned");
   if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
   if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
                                       net->out_act, kValLdMax))
@@ -1408,11 +1436,98 @@ int narde_value_fit(int device, const narde_value_mlp_train* net, int64_t n, con
   k_fit_grad<<<(unsigned)slabs, 2 * kTdBlock, (size_t)P * sizeof(float), st>>>((const uint4*)records, n, tn, target, weight,
                                                                            part, ld_part, slab_loss, v);
   if (const int rc = check_launch("k_fit_grad")) return rc;
-  k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
-  if (const int rc = check_launch("k_td_update")) return rc;
+  if (to_grad) {
+    k_td_fold<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>((int)P, part, ld_part, slabs, grad);
+    if (const int rc = check_launch("k_td_fold")) return rc;
+  } else {
+    k_td_update<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, alpha, part, ld_part, slabs);
+    if (const int rc = check_launch("k_td_update")) return rc;
+  }
   if (!loss) return NARDE_OK;
   k_fit_loss<<<1, 64, 0, st>>>(slab_loss, slabs, loss);
   return check_launch("k_fit_loss");
+}
+
+int narde_value_fit(int device, const narde_value_mlp_train* net, int64_t n, const void* records, const float* target,
+                    const float* weight, float alpha, float* scratch, int64_t scratch_floats, float* v, double* loss,
+                    void* stream) {
+  return value_fit_call(device, net, n, records, target, weight, alpha, scratch, scratch_floats, v, loss, false,
+                        nullptr, stream);
+}
+
+int narde_value_fit_grad(int device, const narde_value_mlp_train* net, int64_t n, const void* records,
+                         const float* target, const float* weight, float* scratch, int64_t scratch_floats, float* v,
+                         double* loss, float* grad, void* stream) {
+  return value_fit_call(device, net, n, records, target, weight, 0.0f, scratch, scratch_floats, v, loss, true, grad,
+                        stream);
+}
+
+// a trained net's description as the optimiser steps check it, and the kernels' view of it
+static int check_opt_net(int device, const narde_value_mlp_train* net, TdNet& tn) {
+  if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
+  if (!net) return fail(NARDE_EINVAL, "NULL argument");
+  if (const int rc = check_mlp_fields(net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->hidden, net->hidden_act,
+                                      net->out_act, kValLdMax))
+    return rc;
+  if (net->w1 && net->ld_w1 < 198) return fail(NARDE_EINVAL, "ld_w1 %lld below 198", (long long)net->ld_w1);
+  tn = TdNet{net->w1t, net->ld_w1t, net->b1, net->w2, net->b2, net->w1, net->ld_w1, net->hidden, net->hidden_act,
+             net->out_act};
+  return NARDE_OK;
+}
+
+static bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0u; }
+
+int narde_value_grad_norm(int device, int hidden, const float* grad, float max_norm, float* out, void* stream) {
+  if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
+  if (!grad || !out) return fail(NARDE_EINVAL, "NULL argument");
+  if (hidden < 1 || hidden > NARDE_VALUE_HIDDEN_MAX)
+    return fail(NARDE_EINVAL, "hidden %d outside 1..%d", hidden, NARDE_VALUE_HIDDEN_MAX);
+  if (!aligned16(grad)) return fail(NARDE_EINVAL, "grad must be 16-B aligned");
+  if (!aligned4(out)) return fail(NARDE_EINVAL, "out must be 4-B aligned");
+  if (!(max_norm >= 0.0f)) return fail(NARDE_EINVAL, "max_norm %g is negative", (double)max_norm);
+  DeviceGuard dg(device);
+  k_opt_norm<<<1, kOptBlock, 0, (hipStream_t)stream>>>((int)td_row_floats(hidden), grad, max_norm, out);
+  return check_launch("k_opt_norm");
+}
+
+int narde_value_sgd_step(int device, const narde_value_mlp_train* net, const float* grad, const float* scale,
+                         float alpha, void* stream) {
+  TdNet tn;
+  if (const int rc = check_opt_net(device, net, tn)) return rc;
+  if (!grad) return fail(NARDE_EINVAL, "NULL argument");
+  if (!aligned16(grad)) return fail(NARDE_EINVAL, "grad must be 16-B aligned");
+  if (!aligned4(scale)) return fail(NARDE_EINVAL, "scale must be 4-B aligned");
+  if (!(alpha >= 0.0f)) return fail(NARDE_EINVAL, "alpha %g is negative", (double)alpha);
+  DeviceGuard dg(device);
+  const int64_t P = td_row_floats(tn.hidden);
+  k_sgd_step<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, (hipStream_t)stream>>>(tn, grad, scale, alpha);
+  return check_launch("k_sgd_step");
+}
+
+int narde_value_adam_step(int device, const narde_value_mlp_train* net, const float* grad, const float* scale,
+                          float* m, float* s, narde_adam_state* state, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, void* stream) {
+  TdNet tn;
+  if (const int rc = check_opt_net(device, net, tn)) return rc;
+  if (!grad || !m || !s || !state) return fail(NARDE_EINVAL, "NULL argument");
+  if (!aligned16(grad) || !aligned16(m) || !aligned16(s)) return fail(NARDE_EINVAL, "grad, m and s must be 16-B aligned");
+  if (!aligned4(scale)) return fail(NARDE_EINVAL, "scale must be 4-B aligned");
+  if (reinterpret_cast<uintptr_t>(state) & 7u) return fail(NARDE_EINVAL, "state must be 8-B aligned");
+  if (!(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f))
+    return fail(NARDE_EINVAL, "beta1 %g, beta2 %g: outside [0, 1)", (double)beta1, (double)beta2);
+  if (!(eps > 0.0f)) return fail(NARDE_EINVAL, "eps %g is not positive", (double)eps);
+  if (!(lr >= 0.0f)) return fail(NARDE_EINVAL, "lr %g is negative", (double)lr);
+  if (!(weight_decay >= 0.0f)) return fail(NARDE_EINVAL, "weight_decay %g is negative", (double)weight_decay);
+  DeviceGuard dg(device);
+  hipStream_t st = (hipStream_t)stream;
+  AdamState* ds = reinterpret_cast<AdamState*>(state);
+  const float keep = 1.0f - lr * weight_decay;
+  const int64_t P = td_row_floats(tn.hidden);
+  k_adam_tick<<<1, 64, 0, st>>>(ds, beta1, beta2);
+  if (const int rc = check_launch("k_adam_tick")) return rc;
+  k_adam_step<<<(unsigned)((P + kTdBlock - 1) / kTdBlock), kTdBlock, 0, st>>>(tn, grad, scale, m, s, ds, lr, beta1, beta2,
+                                                                             eps, keep);
+  return check_launch("k_adam_step");
 }
 
 int narde_playout_targets(int device, int64_t n, int trials, const int32_t* sums, const float* leaf, const void* roots,

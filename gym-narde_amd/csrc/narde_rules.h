@@ -2898,4 +2898,57 @@ NARDE_FN void playout_target(const int32_t* sums, const float* leaf, int trials,
   weight = 1.0f;
 }
 
+// --------------------------------- optimiser steps on a given gradient
+// narde_value_grad_norm's, narde_value_sgd_step's and narde_value_adam_step's
+// arithmetic (kernels_value_optim.h; the host check
+// tests/hostcheck/hostcheck_value_optim.cpp runs the same functions serially).
+// The gradient is the direction the weights move along (theta += alpha grad),
+// a trace row's layout.
+constexpr int kOptBlock = 256;  // narde_value_grad_norm's one workgroup
+
+// narde_value_adam_step's device state; zero bytes before the first step
+struct AdamState {
+  int64_t step;     // t, the steps taken
+  double b1t, b2t;  // beta1^t, beta2^t (as written by step t; unread at t = 0)
+};
+
+// step t - 1 -> t: the count and the running products, in double -- formed in
+// float32, 1 - beta2^t loses about four digits in the first steps
+NARDE_FN void adam_tick(AdamState& S, float beta1, float beta2) {
+  S.b1t = S.step == 0 ? (double)beta1 : S.b1t * (double)beta1;
+  S.b2t = S.step == 0 ? (double)beta2 : S.b2t * (double)beta2;
+  S.step += 1;
+}
+// what every element of step t shares: lr / (1 - beta1^t) and sqrt(1 - beta2^t),
+// formed in double and rounded once
+NARDE_FN void adam_coeffs(const AdamState& S, float lr, float& step_size, float& bc2_sqrt) {
+  step_size = (float)((double)lr / (1.0 - S.b1t));
+  bc2_sqrt = (float)sqrt(1.0 - S.b2t);
+}
+// the gradient element a step takes: scaled by the clip coefficient where one is given
+NARDE_FN float opt_grad(float g, const float* scale) { return scale ? scale[0] * g : g; }
+// plain SGD: k_td_update's apply
+NARDE_FN float sgd_element(float theta, float g, float alpha) { return fmaf(alpha, g, theta); }
+// AdamW, maximising: the decoupled decay (keep = 1 - lr weight_decay, formed by
+// the caller in float), the moments, the step.  m and s are updated in place.
+NARDE_FN float adam_element(float theta, float g, float& m, float& s, float keep, float beta1, float beta2,
+                            float step_size, float bc2_sqrt, float eps) {
+  theta *= keep;
+  m = fmaf(beta1, m, (1.0f - beta1) * g);
+  s = fmaf(beta2, s, ((1.0f - beta2) * g) * g);
+  const float denom = sqrtf(s) / bc2_sqrt + eps;
+  return fmaf(step_size, m / denom, theta);
+}
+// The norm's reduction: kOptBlock lanes, lane l taking elements l, l +
+// kOptBlock, .. in index order in double, then the lanes' sums by halving
+// (lane l += lane l + o, o = kOptBlock / 2 .. 1).  opt_sq_add is a lane's
+// addend, opt_norm_finish what lane 0 makes of the total.
+NARDE_FN double opt_sq_add(double acc, float g) { return fma((double)g, (double)g, acc); }
+// torch.nn.utils.clip_grad_norm_'s coefficient, clamped at 1
+NARDE_FN void opt_norm_finish(double total, float max_norm, float& norm, float& scale) {
+  norm = (float)sqrt(total);
+  const float c = max_norm / (norm + 1e-6f);
+  scale = c < 1.0f ? c : 1.0f;
+}
+
 }  // namespace narde

@@ -168,6 +168,14 @@ SIGNATURES = {
     "narde_value_fit": (_i32, [_i32, ctypes.POINTER(ValueMlpTrain), _i64, _vp, _vp, _vp, ctypes.c_float, _vp, _i64, _vp,
                                _vp, _vp]),
     "narde_playout_targets": (_i32, [_i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "narde_value_td_window_grad": (_i32, [_vp, ctypes.POINTER(ValueMlpTrain), _i32, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                          ctypes.c_float, _vp, _i64, _vp, _vp, _vp]),
+    "narde_value_fit_grad": (_i32, [_i32, ctypes.POINTER(ValueMlpTrain), _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                    _vp]),
+    "narde_value_grad_norm": (_i32, [_i32, _i32, _vp, ctypes.c_float, _vp, _vp]),
+    "narde_value_sgd_step": (_i32, [_i32, ctypes.POINTER(ValueMlpTrain), _vp, _vp, ctypes.c_float, _vp]),
+    "narde_value_adam_step": (_i32, [_i32, ctypes.POINTER(ValueMlpTrain), _vp, _vp, _vp, _vp, _vp, ctypes.c_float,
+                                     ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _vp]),
     "narde_policy_masked_argmax576": (_i32, [_i32, _vp, _i64, _vp, _i64, ctypes.c_float, _u64, _u32,
                                              _i32, _vp, _vp]),
     "narde_policy_masked_argmax576_dev": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _u64, _vp, _i32, _vp,

@@ -35,6 +35,14 @@ playouts of the window's positions (VecNardeEnv.playout), their means as the
 targets (VecNardeEnv.playout_targets), one fit.  LookaheadTargetLearner
  is the same loop with the two-ply values of the window's
 positions (VecNardeEnv.lookahead_records) as the targets.
+
+ValueSGD and ValueAdam are optimiser steps on a given
+gradient row, on the device.  The three windowed learners and ValueFitter take
+optimizer= and grad_hook=: the update then makes the summed gradient
+(narde_value_td_window_grad / narde_value_fit_grad; the direction the plain
+update moves along, theta += alpha grad), calls grad_hook(grad) -- the place
+for an all_reduce over ranks --, and hands it to optimizer.step(grad).  With
+neither they run the plain calls as before.
 """
 import ctypes
 
@@ -54,9 +62,36 @@ def _check_learner(name, env, net, lam):
         raise ValueError("lam must be in [0, 1]")
 
 
+def _check_optimizer(name, env, net, alpha, optimizer, grad_hook, alpha_at_step=False):
+    """The learners' optimizer= and grad_hook=: an optimiser has the step size
+    (alpha must be None with one), is over this net, on this device.
+    alpha_at_step: the caller takes alpha with every step, not here."""
+    if optimizer is None:
+        if grad_hook is not None:
+            raise ValueError(f"{name}: grad_hook needs an optimizer (the plain update has no gradient to hand out)")
+        if alpha is None and not alpha_at_step:
+            raise ValueError(f"{name} needs alpha or an optimizer")
+        return
+    if not isinstance(optimizer, _ValueOptimizer):
+        raise TypeError(f"{name}: optimizer must be a gym_narde.td.ValueSGD or ValueAdam")
+    if alpha is not None:
+        raise ValueError(f"{name}: alpha and an optimizer are mutually exclusive (the optimizer has the step size); "
+                         "pass alpha=None")
+    if optimizer.net is not net:
+        raise ValueError(f"{name}: the optimizer was made for another net")
+    if optimizer.device != env.device:
+        raise ValueError(f"the optimizer is on {optimizer.device}, the env on {env.device}")
+    if grad_hook is not None and not callable(grad_hook):
+        raise TypeError(f"{name}: grad_hook must be callable")
+
+
 def _train_struct(env, net):
     """The ctypes narde_value_mlp_train over the net's live tensors."""
-    t = env.torch
+    return _train_struct_of(env.torch, net)
+
+
+def _train_struct_of(t, net):
+    """_train_struct for a caller without an env (t: the torch module)."""
     net.struct()  # packs _w1t on first use, checks the parameters
     w = net.l1.weight
     if w.dtype != t.float32 or not w.is_contiguous():
@@ -66,19 +101,157 @@ def _train_struct(env, net):
                               OUT_ACTS[net.out_act], w.data_ptr(), w.stride(0))
 
 
+class _ValueOptimizer:
+    """What ValueSGD and ValueAdam share: the net's train struct, the gradient
+    check, the optional norm clip (narde_value_grad_norm), the stream."""
+
+    def __init__(self, net, max_grad_norm):
+        import torch as t
+
+        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+            raise TypeError(f"{type(self).__name__} needs a gym_narde.value_net.ValueMLP")
+        if not net.l1.weight.is_cuda:
+            raise ValueError(f"{type(self).__name__} needs a net on a GPU device: the steps are device kernels")
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError("max_grad_norm must be None or >= 0")
+        self.torch, self.net, self.device = t, net, net.l1.weight.device
+        self.rows = 200 * net.hidden + 1
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        # (norm, clip coefficient) of the last clipped step
+        self.norm = None if max_grad_norm is None else t.zeros(2, dtype=t.float32, device=self.device)
+        self._mlp = _train_struct_of(t, net)
+        self._lib = _lib.load()
+
+    def _s(self):
+        return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _scale(self, grad):
+        """Checks grad; with a max_grad_norm the norm launch, and the pointer
+        of its coefficient on the device (None: no clip)."""
+        t = self.torch
+        if (not isinstance(grad, t.Tensor) or grad.dtype != t.float32 or grad.device != self.device
+                or not grad.is_contiguous() or tuple(grad.shape) != (self.rows,)):
+            raise ValueError(f"grad must be a contiguous ({self.rows},) float32 tensor on {self.device}")
+        if self.norm is None:
+            return None
+        _lib.check(self._lib.narde_value_grad_norm(self.device.index, self.net.hidden, _lib.ptr(grad),
+                                                   self.max_grad_norm, _lib.ptr(self.norm), self._s()),
+                   "narde_value_grad_norm")
+        return ctypes.c_void_p(self.norm.data_ptr() + 4)
+
+    def _load(self, state, names):
+        for name in names:
+            src, dst = state[name], getattr(self, name)
+            if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                raise ValueError(f"{name}: expected {tuple(dst.shape)} {dst.dtype}, got {tuple(src.shape)} {src.dtype}")
+            dst.copy_(src)  # in place: a captured graph keeps its pointers
+
+
+class ValueSGD(_ValueOptimizer):
+    """theta += alpha grad on the device (narde_value_sgd_step): the plain
+    updates' own apply, so a learner with ValueSGD(net, alpha) and no clip moves
+    the weights to the plain call's bits.  max_grad_norm: clip the row's
+    Euclidean norm to it first (torch.nn.utils.clip_grad_norm_'s coefficient).
+    step() is stream-ordered and graph-capturable, writes net._w1t and the
+    module's parameters alike (no pack()), and makes no synchronise."""
+
+    def __init__(self, net, alpha, max_grad_norm=None):
+        super().__init__(net, max_grad_norm)
+        if not float(alpha) >= 0.0:
+            raise ValueError("alpha must be >= 0")
+        self.alpha = float(alpha)
+        self.steps = self.torch.zeros((), dtype=self.torch.int64, device=self.device)
+
+    def step(self, grad):
+        scale = self._scale(grad)
+        _lib.check(self._lib.narde_value_sgd_step(self.device.index, ctypes.byref(self._mlp), _lib.ptr(grad), scale,
+                                                  self.alpha, self._s()), "narde_value_sgd_step")
+        self.steps += 1
+
+    def state_dict(self):
+        return {"steps": self.steps.clone()}
+
+    def load_state_dict(self, state):
+        self._load(state, ("steps",))
+
+    def memory_bytes(self):
+        """Device memory the optimiser owns."""
+        return 8 + (0 if self.norm is None else 8)
+
+
+class ValueAdam(_ValueOptimizer):
+    """torch.optim.AdamW(maximize=True) on the gradient row, on the device
+    (narde_value_adam_step); weight_decay = 0 is the papers' Adam.  Owns the
+    moments m and s, (200 H + 1,) float32 in the row's layout, and the device
+    state -- the step count and the running products beta1^t, beta2^t in
+    double --, which a step advances on the device: a captured graph replays
+    successive steps.  max_grad_norm: as ValueSGD's.  step() is stream-ordered
+    and graph-capturable, writes net._w1t and the module's parameters alike
+    (no pack()), and makes no synchronise."""
+
+    def __init__(self, net, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=None):
+        super().__init__(net, max_grad_norm)
+        t = self.torch
+        b1, b2 = (float(b) for b in betas)
+        if not float(lr) >= 0.0:
+            raise ValueError("lr must be >= 0")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError("betas must be in [0, 1)")
+        if not float(eps) > 0.0:
+            raise ValueError("eps must be > 0")
+        if not float(weight_decay) >= 0.0:
+            raise ValueError("weight_decay must be >= 0")
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (b1, b2), float(eps), float(weight_decay)
+        self.m = t.zeros(self.rows, dtype=t.float32, device=self.device)
+        self.s = t.zeros(self.rows, dtype=t.float32, device=self.device)
+        self.state = t.zeros(3, dtype=t.int64, device=self.device)  # narde_adam_state: the count, two doubles
+
+    @property
+    def steps(self):
+        """The steps taken: a 0-d int64 view of the device state."""
+        return self.state[0]
+
+    def beta_pows(self):
+        """(beta1^t, beta2^t) as the last step left them: a float64 view."""
+        return self.state[1:].view(self.torch.float64)
+
+    def step(self, grad):
+        scale = self._scale(grad)
+        _lib.check(self._lib.narde_value_adam_step(self.device.index, ctypes.byref(self._mlp), _lib.ptr(grad), scale,
+                                                   _lib.ptr(self.m), _lib.ptr(self.s), _lib.ptr(self.state), self.lr,
+                                                   self.betas[0], self.betas[1], self.eps, self.weight_decay,
+                                                   self._s()), "narde_value_adam_step")
+
+    def state_dict(self):
+        return {"m": self.m.clone(), "s": self.s.clone(), "state": self.state.clone()}
+
+    def load_state_dict(self, state):
+        self._load(state, ("m", "s", "state"))
+
+    def memory_bytes(self):
+        """Device memory the optimiser owns."""
+        return 8 * self.rows + 24 + (0 if self.norm is None else 8)
+
+
 class WindowTDLambdaLearner:
     """env: a VecNardeEnv (either rule set) with autoreset; net: a ValueMLP on
     its device.  alpha: step size; lam: the return's decay; plies: the
     window K; gamma: the discount; epsilon: the explore probability of the
-    play (None: greedy); seed: the explore draws' key."""
+    play (None: greedy); seed: the explore draws' key.  optimizer: a ValueSGD
+    or ValueAdam over the net, alpha then None -- update() makes the window's
+    gradient, calls grad_hook(grad) if given (the learner's own (200 H + 1,)
+    tensor; edit it in place) and hands it to optimizer.step()."""
 
-    def __init__(self, env, net, alpha, lam, plies, gamma=1.0, epsilon=None, seed=0):
+    def __init__(self, env, net, alpha, lam, plies, gamma=1.0, epsilon=None, seed=0, optimizer=None, grad_hook=None):
         t = env.torch
         _check_learner("WindowTDLambdaLearner", env, net, lam)
+        _check_optimizer("WindowTDLambdaLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1:
             raise ValueError("plies must be >= 1")
         self.env, self.net, self.plies = env, net, int(plies)
-        self.alpha, self.lam, self.gamma, self.seed = float(alpha), float(lam), float(gamma), int(seed)
+        self.alpha = None if alpha is None else float(alpha)
+        self.lam, self.gamma, self.seed = float(lam), float(gamma), int(seed)
+        self.optimizer, self.grad_hook, self.grad = optimizer, grad_hook, None
         z = dict(device=env.device)
         make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
         self.bufs = make(self.plies, records=True)
@@ -103,11 +276,31 @@ class WindowTDLambdaLearner:
 
     def update(self):
         """One weight update from the window play() recorded."""
+        if self.optimizer is not None:
+            grad = self.gradient()
+            if self.grad_hook is not None:
+                self.grad_hook(grad)
+            self.optimizer.step(grad)
+            return
         b = self.bufs
         self.env.handle.call("narde_value_td_window", ctypes.byref(self._mlp), self.plies, _lib.ptr(b["records"]),
                              _lib.ptr(b["reward"]), _lib.ptr(b["terminated"]), _lib.ptr(b["truncated"]), self.alpha,
                              self.lam, self.gamma, _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.delta),
                              self.env._s())
+
+    def gradient(self):
+        """sum_e sum_k G_k grad_theta v(s_k) of the window play() recorded, under
+        the weights as they are: (200 H + 1,) float32 in a trace row's layout
+        (the learner's own tensor, rewritten by the next call).  Moves no
+        weight; delta and values() are the plain update's."""
+        b, t = self.bufs, self.env.torch
+        if self.grad is None:
+            self.grad = t.zeros(200 * self.net.hidden + 1, dtype=t.float32, device=self.env.device)
+        self.env.handle.call("narde_value_td_window_grad", ctypes.byref(self._mlp), self.plies, _lib.ptr(b["records"]),
+                             _lib.ptr(b["reward"]), _lib.ptr(b["terminated"]), _lib.ptr(b["truncated"]), self.lam,
+                             self.gamma, _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.delta),
+                             _lib.ptr(self.grad), self.env._s())
+        return self.grad
 
     def step(self):
         """K plies of self-play and their one update.  Returns (reward,
@@ -129,6 +322,8 @@ class WindowTDLambdaLearner:
         own = [x for x in self.bufs.values() if x is not None] + [self.delta, self.scratch]
         if self._roll_scratch is not None:
             own.append(self._roll_scratch)
+        if self.grad is not None:
+            own.append(self.grad)
         return sum(x.numel() * x.element_size() for x in own)
 
 
@@ -138,9 +333,11 @@ class ValueFitter:
     and stream; its positions are not touched); net: a ValueMLP on that
     device; n: the most samples a call takes.  Owns the scratch and the train
     struct; after a step net(feat), state_dict() and scored_afterstates(net)
-    agree with no pack(), as with the TD learners."""
+    agree with no pack(), as with the TD learners.  optimizer: a ValueSGD or
+    ValueAdam over the net -- step() then takes no alpha: it makes the
+    gradient, calls grad_hook(grad) if given and hands it to optimizer.step()."""
 
-    def __init__(self, env, net, n):
+    def __init__(self, env, net, n, optimizer=None, grad_hook=None):
         t = env.torch
         if not (hasattr(net, "struct") and hasattr(net, "pack")):
             raise TypeError("ValueFitter needs a gym_narde.value_net.ValueMLP")
@@ -148,7 +345,9 @@ class ValueFitter:
             raise ValueError(f"the net is on {net.l1.weight.device}, the env on {env.device}")
         if int(n) < 1:
             raise ValueError("n must be >= 1")
+        _check_optimizer("ValueFitter", env, net, None, optimizer, grad_hook, alpha_at_step=True)
         self.env, self.net, self.n = env, net, int(n)
+        self.optimizer, self.grad_hook, self.grad = optimizer, grad_hook, None
         z = dict(device=env.device)
         self.scratch = t.empty(_lib.value_fit_scratch_floats(self.n, net.hidden), dtype=t.float32, **z)
         self.v = t.zeros(self.n, dtype=t.float32, **z)
@@ -156,7 +355,7 @@ class ValueFitter:
         self._m = 0
         self._mlp = _train_struct(env, net)
 
-    def step(self, records, target, weight=None, *, alpha):
+    def step(self, records, target, weight=None, *, alpha=None):
         """theta += alpha sum_i w_i (target_i - v(s_i)) grad v(s_i): a sum, not
         a mean (divide alpha by the weights' sum for that).  records (m, 8)
         int32 (state_records(), a records rollout's, recorded rows'), m <= n;
@@ -164,7 +363,33 @@ class ValueFitter:
         or None (all 1) -- where it is 0 the target is never read.  Returns
         the device tensor loss (2,) float64 = (sum w e^2, sum w) under the
         weights the call found (the fitter's own, rewritten by the next call).
-        No synchronise."""
+        No synchronise.  A fitter with an optimizer takes no alpha: the sum
+        goes through grad_hook to optimizer.step()."""
+        if self.optimizer is None:
+            if alpha is None:
+                raise TypeError("ValueFitter.step() needs alpha= (the fitter has no optimizer)")
+            return self._call(records, target, weight, float(alpha), False)
+        if alpha is not None:
+            raise ValueError("ValueFitter.step(): alpha and an optimizer are mutually exclusive (the optimizer has the "
+                             "step size)")
+        grad = self.gradient(records, target, weight)
+        if self.grad_hook is not None:
+            self.grad_hook(grad)
+        self.optimizer.step(grad)
+        return self.loss
+
+    def gradient(self, records, target, weight=None):
+        """sum_i w_i (target_i - v(s_i)) grad v(s_i) under the weights as they
+        are: (200 H + 1,) float32 in a trace row's layout (the fitter's own
+        tensor, rewritten by the next call).  Moves no weight; loss and
+        values() are step()'s."""
+        t = self.env.torch
+        if self.grad is None:
+            self.grad = t.zeros(200 * self.net.hidden + 1, dtype=t.float32, device=self.env.device)
+        self._call(records, target, weight, 0.0, True)
+        return self.grad
+
+    def _call(self, records, target, weight, alpha, to_grad):
         t, env = self.env.torch, self.env
         if (not isinstance(records, t.Tensor) or records.dtype != t.int32 or records.device != env.device
                 or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8):
@@ -174,16 +399,24 @@ class ValueFitter:
             raise ValueError(f"{m} samples: the fitter was made for 1 .. {self.n}")
         target = env._dev(target, t.float32, (m,))
         weight = None if weight is None else env._dev(weight, t.float32, (m,))
-        _lib.check(env.handle.lib.narde_value_fit(env.device.index, ctypes.byref(self._mlp), m, _lib.ptr(records),
-                                                  _lib.ptr(target), _lib.ptr(weight), float(alpha),
-                                                  _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.v),
-                                                  _lib.ptr(self.loss), env._s()), "narde_value_fit")
+        if to_grad:
+            _lib.check(env.handle.lib.narde_value_fit_grad(env.device.index, ctypes.byref(self._mlp), m,
+                                                           _lib.ptr(records), _lib.ptr(target), _lib.ptr(weight),
+                                                           _lib.ptr(self.scratch), self.scratch.numel(),
+                                                           _lib.ptr(self.v), _lib.ptr(self.loss), _lib.ptr(self.grad),
+                                                           env._s()), "narde_value_fit_grad")
+        else:
+            _lib.check(env.handle.lib.narde_value_fit(env.device.index, ctypes.byref(self._mlp), m, _lib.ptr(records),
+                                                      _lib.ptr(target), _lib.ptr(weight), float(alpha),
+                                                      _lib.ptr(self.scratch), self.scratch.numel(), _lib.ptr(self.v),
+                                                      _lib.ptr(self.loss), env._s()), "narde_value_fit")
         self._m, self._keep = m, (records, target, weight)
         return self.loss
 
     def evaluate(self, records, target, weight=None):
-        """step() with alpha = 0: the loss and values(), no weight bit moved."""
-        return self.step(records, target, weight, alpha=0.0)
+        """The plain call with alpha = 0: the loss and values(), no weight bit
+        moved (with or without an optimizer)."""
+        return self._call(records, target, weight, 0.0, False)
 
     def values(self):
         """v (m,) of the last call: v(s_i) under the weights it found."""
@@ -191,7 +424,8 @@ class ValueFitter:
 
     def memory_bytes(self):
         """Device memory the fitter owns."""
-        return sum(x.numel() * x.element_size() for x in (self.scratch, self.v, self.loss))
+        own = [self.scratch, self.v, self.loss] + ([] if self.grad is None else [self.grad])
+        return sum(x.numel() * x.element_size() for x in own)
 
 
 class PlayoutTargetLearner:
@@ -210,18 +444,21 @@ class PlayoutTargetLearner:
     plies deep instead of a Monte-Carlo return.  epsilon: the explore
     probability of the self-play (None: greedy); common_dice: playout()'s.
     The playouts' seed is seed + the count of windows played: the same
-    arguments and the same number of steps give the same weight bits."""
+    arguments and the same number of steps give the same weight bits.
+    optimizer, grad_hook: ValueFitter's (alpha then None)."""
 
     def __init__(self, env, net, alpha, plies, trials, every=1, max_plies=400, leaf=False, playout_net=None,
-                 epsilon=None, common_dice=False, seed=0):
+                 epsilon=None, common_dice=False, seed=0, optimizer=None, grad_hook=None):
         t = env.torch
         _check_learner("PlayoutTargetLearner", env, net, 0.0)
+        _check_optimizer("PlayoutTargetLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1 or int(trials) < 1 or int(every) < 1 or int(max_plies) < 1:
             raise ValueError("plies, trials, every and max_plies must be >= 1")
         self.env, self.net, self.plies, self.trials = env, net, int(plies), int(trials)
         self.every, self.max_plies, self.leaf = int(every), int(max_plies), bool(leaf)
         self.playout_net = net if playout_net is None else playout_net
-        self.alpha, self.seed, self.common_dice = float(alpha), int(seed), bool(common_dice)
+        self.alpha = None if alpha is None else float(alpha)
+        self.seed, self.common_dice = int(seed), bool(common_dice)
         self.windows = 0
         z = dict(device=env.device)
         B, M = env.num_envs, -(-self.plies // self.every)
@@ -232,7 +469,7 @@ class PlayoutTargetLearner:
         self.result = None  # the playouts' PlayoutResult, made by the first targets()
         self.target = t.zeros(N, dtype=t.float32, **z)
         self.weight = t.zeros(N, dtype=t.float32, **z)
-        self.fitter = ValueFitter(env, net, N)
+        self.fitter = ValueFitter(env, net, N, optimizer=optimizer, grad_hook=grad_hook)
         self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
         self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
         self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
@@ -300,15 +537,17 @@ class LookaheadTargetLearner:
     position); update() -- one narde_value_fit of those roots at step size
     alpha (a sum over the roots).  epsilon: the explore probability of the
     self-play (None: greedy).  Nothing is drawn besides the self-play: the same
-    arguments and the same number of steps give the same weight bits."""
+    arguments and the same number of steps give the same weight bits.
+    optimizer, grad_hook: ValueFitter's (alpha then None)."""
 
-    def __init__(self, env, net, alpha, plies, every=1, epsilon=None, seed=0):
+    def __init__(self, env, net, alpha, plies, every=1, epsilon=None, seed=0, optimizer=None, grad_hook=None):
         t = env.torch
         _check_learner("LookaheadTargetLearner", env, net, 0.0)
+        _check_optimizer("LookaheadTargetLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1 or int(every) < 1:
             raise ValueError("plies and every must be >= 1")
         self.env, self.net, self.plies, self.every = env, net, int(plies), int(every)
-        self.alpha, self.seed = float(alpha), int(seed)
+        self.alpha, self.seed = None if alpha is None else float(alpha), int(seed)
         self.windows = 0
         z = dict(device=env.device)
         B, M = env.num_envs, -(-self.plies // self.every)
@@ -318,7 +557,7 @@ class LookaheadTargetLearner:
         self.roots = t.zeros((N, 8), dtype=t.int32, **z)
         self.target = t.zeros(N, dtype=t.float32, **z)
         self.weight = t.zeros(N, dtype=t.float32, **z)
-        self.fitter = ValueFitter(env, net, N)
+        self.fitter = ValueFitter(env, net, N, optimizer=optimizer, grad_hook=grad_hook)
         self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
         self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
         self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)

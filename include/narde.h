@@ -981,6 +981,75 @@ int narde_value_fit(int device, const narde_value_mlp_train *net, int64_t n, con
 int narde_playout_targets(int device, int64_t n, int trials, const int32_t *sums, const float *leaf,
                           const void *roots, float *target, float *weight, void *stream);
 
+/* The gradient forms of the two batch updates:
+ * narde_value_td_window and narde_value_fit without alpha and with one more
+ * output.  grad f32[P], P = 200 * hidden + 1, 16-B aligned, a trace row's
+ * layout (above): grad[c * hidden + h] for column c < 198, then b1's, w2's,
+ * b2's.  grad[p] is exactly the sum the plain call multiplies by alpha -- the
+ * slabs' partial rows added in slab order, from 0.0f --: the direction the
+ * plain update moves along, theta += alpha * grad.  Neither the weights nor
+ * the mirror are written; v, G, delta and loss come out with the plain call's
+ * bits; the scratch macros are the plain calls'.  narde_value_sgd_step with
+ * scale == NULL behind one of these leaves the plain call's weight bits.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable once the
+ * device has seen one call.  NARDE_EINVAL before any device call: the plain
+ * call's cases, grad NULL or not 16-B aligned. */
+int narde_value_td_window_grad(narde_env *env, const narde_value_mlp_train *net, int plies,
+                               const void *records, const int32_t *reward, const uint8_t *terminated,
+                               const uint8_t *truncated, float lam, float gamma, float *scratch,
+                               int64_t scratch_floats, float *delta, float *grad, void *stream);
+int narde_value_fit_grad(int device, const narde_value_mlp_train *net, int64_t n, const void *records,
+                         const float *target, const float *weight, float *scratch,
+                         int64_t scratch_floats, float *v, double *loss, float *grad, void *stream);
+
+/* Optimiser steps on a given gradient f32[P] in that layout (the calls above
+ * make one; a caller may average it over ranks or edit it first).  Stateless:
+ * a device, no handle.  All three are stream-ordered, allocate nothing, do not
+ * synchronise and are graph-capturable; none uses a float atomic, so the same
+ * inputs give the same bits.
+ *
+ * narde_value_grad_norm: out[0] = the Euclidean norm of grad, out[1] =
+ * min(1, max_norm / (out[0] + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s
+ * coefficient.  One workgroup; the squares are added in double in one fixed
+ * order, the norm rounded to float once, the coefficient formed in float.
+ *
+ * narde_value_sgd_step: theta[p] = fmaf(alpha, g, theta[p]) into w1t, b1, w2,
+ * b2 and the mirror (the same bits to both); g = grad[p] when scale is NULL,
+ * scale[0] * grad[p] otherwise -- scale a DEVICE float, out + 1 of the norm
+ * call for a clipped step.
+ *
+ * narde_value_adam_step: torch.optim.AdamW(maximize=True) on the row (the
+ * papers' Adam is weight_decay = 0).  m and s f32[P], the moments, and state,
+ * a narde_adam_state, are the caller's device memory, all zero bytes before
+ * the first step.  A call advances state on the device -- step += 1, the
+ * running products beta1^t and beta2^t in double (in float32 1 - beta2^t
+ * loses about four digits in the first steps) -- in a one-thread launch in
+ * front of the element kernel, so a captured graph replays successive steps.
+ * Then per element, g as above:
+ *   theta *= 1 - lr * weight_decay
+ *   m = beta1 * m + (1 - beta1) * g;  s = beta2 * s + (1 - beta2) * g * g
+ *   theta += (lr / (1 - beta1^t)) * m / (sqrt(s) / sqrt(1 - beta2^t) + eps)
+ * the two bias corrections formed in double and rounded to float once.
+ *
+ * NARDE_EINVAL before any device call: a negative device, a NULL grad, out,
+ * net, weight array, m, s or state, grad, m or s not 16-B aligned, out or
+ * scale not 4-B aligned, state not 8-B aligned, hidden outside
+ * 1..NARDE_VALUE_HIDDEN_MAX, the net cases of narde_value_td_trace, beta1 or
+ * beta2 outside [0, 1), eps <= 0, a negative (or NaN) max_norm, alpha, lr or
+ * weight_decay. */
+typedef struct narde_adam_state {
+  int64_t step;     /* the steps taken */
+  double beta1_pow; /* beta1^step */
+  double beta2_pow; /* beta2^step */
+} narde_adam_state;
+int narde_value_grad_norm(int device, int hidden, const float *grad, float max_norm, float *out,
+                          void *stream);
+int narde_value_sgd_step(int device, const narde_value_mlp_train *net, const float *grad,
+                         const float *scale, float alpha, void *stream);
+int narde_value_adam_step(int device, const narde_value_mlp_train *net, const float *grad,
+                          const float *scale, float *m, float *s, narde_adam_state *state, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, void *stream);
+
 /* Masked epsilon-greedy over the 576 codes (the policy of
  * train_deepq_pytorch.py:411-600, batched; stateless): q f32[n][ldq]
  * (ldq >= 576) Q-values, mask u64[n][9] legal codes (the two mask entry
