@@ -58,6 +58,9 @@
 //   kernels_value_fit.h  the supervised fit of given records to given float
 //                       targets, and the playout targets (k_fit_grad,
 //                       k_fit_loss, k_playout_targets)
+//   kernels_league.h    the two value rollouts with a net per env and colour
+//                       from a table (k_net_table_write,
+//                       k_value_rollout_league, k_turn_value_rollout_league)
 // This file keeps the handle, the host-side checks and every C entry point.
 // The DQN learner kernels are a second translation unit (dqn_learner.hip);
 // host_common.h: the host helpers the two share.
@@ -97,6 +100,7 @@ thread_local char narde_host::g_err[512] = "";
 #include "kernels_td_window.h"
 #include "kernels_value_fit.h"
 #include "kernels_value_optim.h"
+#include "kernels_league.h"
 
 namespace {
 
@@ -1008,6 +1012,112 @@ int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net
                              uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* stream) {
   return narde_turn_value_rollout_records(e, plies, net_white, net_black, epsilon, seed, tag, dice, play, value, reward,
                                           terminated, truncated, scratch, scratch_bytes, nullptr, stream);
+}
+
+// ---------------------------------------------------------------- leagues
+static_assert(kLeagueBatch <= 64 && NARDE_LEAGUE_NETS_MAX % kLeagueBatch == 0, "k_net_table_write's batches");
+
+int narde_net_table(int device, int n_nets, const narde_value_mlp* nets, void* table, int64_t table_bytes,
+                    void* stream) {
+  if (device < 0) return fail(NARDE_EINVAL, "device %d is negative", device);
+  if (!nets || !table) return fail(NARDE_EINVAL, "NULL argument");
+  if (n_nets < 1 || n_nets > NARDE_LEAGUE_NETS_MAX)
+    return fail(NARDE_EINVAL, "n_nets %d outside 1..%d", n_nets, NARDE_LEAGUE_NETS_MAX);
+  if (!aligned16(table)) return fail(NARDE_EINVAL, "table must be 16-B aligned");
+  if (table_bytes < NARDE_LEAGUE_TABLE_BYTES(n_nets))
+    return fail(NARDE_EINVAL, "table_bytes %lld below NARDE_LEAGUE_TABLE_BYTES(%d) = %lld", (long long)table_bytes,
+                n_nets, (long long)NARDE_LEAGUE_TABLE_BYTES(n_nets));
+  for (int i = 0; i < n_nets; ++i) {
+    ValNet vn;
+    if (const int rc = check_value_mlp(&nets[i], 1, nullptr, kValLdMax, vn)) {
+      char why[sizeof g_err];
+      snprintf(why, sizeof why, "%s", g_err);
+      return fail(rc, "net %d: %.400s", i, why);
+    }
+  }
+  DeviceGuard dg(device);
+  for (int i0 = 0; i0 < n_nets; i0 += kLeagueBatch) {
+    const int count = n_nets - i0 < kLeagueBatch ? n_nets - i0 : kLeagueBatch;
+    LeagueBatch b{};
+    for (int j = 0; j < count; ++j) {
+      const narde_value_mlp& m = nets[i0 + j];
+      b.n[j] = LeagueNet{m.w1t, m.ld_w1t, m.b1, m.w2, m.b2, m.hidden, m.hidden_act, m.out_act, 0};
+    }
+    k_net_table_write<<<1, 64, 0, (hipStream_t)stream>>>(b, count, static_cast<LeagueNet*>(table) + i0);
+    if (const int rc = check_launch("k_net_table_write")) return rc;
+  }
+  return NARDE_OK;
+}
+
+namespace {
+
+// The league rollouts' (narde_value_rollout_league,
+// narde_turn_value_rollout_league) checks: check_rollout_nets' with the table
+// and the two index arrays in place of the nets
+int check_league(const narde_env* e, int plies, const void* table, int n_nets, const int32_t* white,
+                 const int32_t* black, const float* epsilon, const int64_t* tag, const void* column, unsigned align,
+                 const char* misaligned) {
+  if (!e) return fail(NARDE_EINVAL, "NULL handle");
+  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  if (!table || !white || !black) return fail(NARDE_EINVAL, "NULL argument");
+  if (!aligned16(table)) return fail(NARDE_EINVAL, "table must be 16-B aligned");
+  if ((reinterpret_cast<uintptr_t>(white) | reinterpret_cast<uintptr_t>(black)) & 3u)
+    return fail(NARDE_EINVAL, "white and black must be 4-B aligned");
+  if (n_nets < 1 || n_nets > NARDE_LEAGUE_NETS_MAX)
+    return fail(NARDE_EINVAL, "n_nets %d outside 1..%d", n_nets, NARDE_LEAGUE_NETS_MAX);
+  if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
+  if (reinterpret_cast<uintptr_t>(column) % align) return fail(NARDE_EINVAL, "%s", misaligned);
+  return NARDE_OK;
+}
+
+}  // namespace
+
+int narde_value_rollout_league(narde_env* e, int plies, const void* table, int n_nets, const int32_t* white,
+                               const int32_t* black, const float* epsilon, uint64_t seed, const int64_t* tag,
+                               uint8_t* dice, int16_t* actions, float* value, int32_t* reward, uint8_t* terminated,
+                               uint8_t* truncated, void* records, void* stream) {
+  if (const int rc = check_league(e, plies, table, n_nets, white, black, epsilon, tag, actions, 4,
+                                  "actions must be 4-B aligned"))
+    return rc;
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
+                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated,
+                 (uint4*)records};
+  const LeagueArgs lg{static_cast<const LeagueNet*>(table), n_nets, white, black};
+  if (records)
+    k_value_rollout_league<true><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, lg);
+  else
+    k_value_rollout_league<false><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, lg);
+  return check_launch("k_value_rollout_league");
+}
+
+int narde_turn_value_rollout_league(narde_env* e, int plies, const void* table, int n_nets, const int32_t* white,
+                                    const int32_t* black, const float* epsilon, uint64_t seed, const int64_t* tag,
+                                    uint8_t* dice, int8_t* play, float* value, int32_t* reward, uint8_t* terminated,
+                                    uint8_t* truncated, void* scratch, int64_t scratch_bytes, void* records,
+                                    void* stream) {
+  if (const int rc = check_league(e, plies, table, n_nets, white, black, epsilon, tag, play, 8,
+                                  "play must be 8-B aligned"))
+    return rc;
+  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
+  if (pieces < 1)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
+                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
+  DeviceGuard dg(e->device);
+  const int64_t waves = pieces < e->n ? pieces : e->n;
+  const TvrArgs a{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
+                  (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
+                  truncated, (uint8_t*)scratch, (uint4*)records};
+  const LeagueArgs lg{static_cast<const LeagueNet*>(table), n_nets, white, black};
+  if (records)
+    k_turn_value_rollout_league<true><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, lg);
+  else
+    k_turn_value_rollout_league<false><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, lg);
+  return check_launch("k_turn_value_rollout_league");
 }
 
 int narde_state_records(int device, int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* first_turn,

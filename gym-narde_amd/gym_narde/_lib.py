@@ -60,6 +60,14 @@ def turn_rollout_scratch_bytes(waves):
     return 83536 * int(waves)
 
 
+LEAGUE_NETS_MAX = 64  # NARDE_LEAGUE_NETS_MAX
+
+
+def league_table_bytes(n_nets):
+    """NARDE_LEAGUE_TABLE_BYTES: narde_net_table's table, an entry a net."""
+    return 64 * int(n_nets)
+
+
 PLAYOUT_COMMON_DICE = 1  # NARDE_PLAYOUT_COMMON_DICE
 TOPK_MAX = 64  # NARDE_TOPK_MAX
 RECORD_NONE_WORD6 = 0xFF  # NARDE_RECORD_NONE_WORD6
@@ -144,6 +152,11 @@ SIGNATURES = {
                                         _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "narde_turn_value_rollout_records": (_i32, [_vp, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _vp, _u64,
                                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "narde_net_table": (_i32, [_i32, _i32, ctypes.POINTER(ValueMlp), _vp, _i64, _vp]),
+    "narde_value_rollout_league": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp]),
+    "narde_turn_value_rollout_league": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp, _vp, _i64, _vp, _vp]),
     "narde_state_records": (_i32, [_i32, _i64, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "narde_value_playout": (_i32, [_vp, _i64, _vp, _i32, _i32, ctypes.POINTER(ValueMlp), ctypes.POINTER(ValueMlp), _u64,
                                    _i64, _i32, _vp, _vp, _vp, _vp, _vp]),

@@ -21,6 +21,9 @@ play_match() answers "is net A better than net B, or than random play?":
 whole games in one launch a colour assignment (VecNardeEnv.value_rollout());
 play_turn_match() is the same on a rules="full4" env
 (VecNardeEnv.turn_value_rollout()).
+play_league() ranks N nets, random play included, by a whole round-robin in
+one launch (VecNardeEnv.value_rollout_league() /
+turn_value_rollout_league(): a net per env and colour from a table).
 """
 
 
@@ -265,3 +268,113 @@ def playout_values(env, roots, net, trials, max_plies=1000, seed=0, id_base=0, c
     res = env.playout(roots, trials, net, max_plies=max_plies, seed=seed, id_base=id_base, common_dice=common_dice,
                       leaf=truncated)
     return res.mean(truncated=truncated), res.stderr()
+
+
+def league_pairs(n, random=False, self_play=False):
+    """The ordered pairs (white, black) of a round-robin over nets 0 .. n - 1:
+    every i != j, white-major; random: index -1 -- the random-legal policy --
+    joins as one more participant, last; self_play: (i, i) for every net too
+    (in its place of the white-major order)."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("n must be >= 1")
+    who = list(range(n)) + ([-1] if random else [])
+    return [(w, b) for w in who for b in who if w != b or (self_play and w >= 0)]
+
+
+def league_result(stats, white, black, n, random=False):
+    """A league launch's per-env statistics as pairing matrices: pure host
+    arithmetic.  stats: (B, 3) integers, env.stats()'s (games, white's points,
+    black's points); white, black: the (B,) indices the launch was given; n:
+    the number of nets.  An index outside 0 .. n - 1 is the random participant
+    (random=True: it is the matrices' last row and column; otherwise a
+    ValueError).
+    Returns a dict: games, points_white, points_black -- int64 (P, P), indexed
+    [white][black], P = n + random --; margin (P, P) float64, margin[i][j] =
+    i's points a game over j with both colour assignments pooled, NaN where
+    the two played no game (margin[i][j] == -margin[j][i]); stderr_bound (P,
+    P), 2 / sqrt(the pooled games): a game gives a side 0, 1 or 2 points, so
+    that bounds the margin's standard error; score (P,), the mean of row i of
+    margin over the opponents i has games against (NaN with none)."""
+    import numpy as np
+
+    stats = np.asarray(stats, dtype=np.int64)
+    white = np.asarray(white, dtype=np.int64).reshape(-1)
+    black = np.asarray(black, dtype=np.int64).reshape(-1)
+    n = int(n)
+    if stats.ndim != 2 or stats.shape[1] != 3 or white.shape[0] != stats.shape[0] or black.shape[0] != stats.shape[0]:
+        raise ValueError("stats must be (B, 3), white and black (B,)")
+    P = n + (1 if random else 0)
+    wi = np.where((white >= 0) & (white < n), white, n)
+    bi = np.where((black >= 0) & (black < n), black, n)
+    if not random and ((wi == n).any() or (bi == n).any()):
+        raise ValueError("an index outside 0 .. n - 1 is the random participant: pass random=True")
+    out = {}
+    for k, name in enumerate(("games", "points_white", "points_black")):
+        m = np.zeros((P, P), dtype=np.int64)
+        np.add.at(m, (wi, bi), stats[:, k])
+        out[name] = m
+    g, pw, pb = out["games"], out["points_white"], out["points_black"]
+    pooled = (g + g.T).astype(np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out["margin"] = np.where(pooled > 0, (pw + pb.T - pb - pw.T) / pooled, np.nan)
+        out["stderr_bound"] = np.where(pooled > 0, 2.0 / np.sqrt(pooled), np.nan)
+    score = np.full(P, np.nan)
+    for i in range(P):
+        has = (pooled[i] > 0) & (np.arange(P) != i)
+        if has.any():
+            score[i] = out["margin"][i][has].mean()
+    out["score"] = score
+    return out
+
+
+def play_league(env, nets, plies, random=False, self_play=False, epsilon=None, seed=0, pairs=None):
+    """A whole round-robin in one launch, on either rule set (DESIGN.md
+    section 27): env e plays the pair e mod len(pairs) of league_pairs(len(nets),
+    random, self_play) -- or of `pairs`, a list of (white, black) indices into
+    nets, -1 the random-legal policy -- as (white, black) for every game it
+    plays.  env.reset(), one value_rollout_league() / turn_value_rollout_league()
+    launch of `plies` plies with every per-ply output off, then
+    league_result(env.stats(), ...).  Games still running at the launch's end
+    do not count, and a game the TimeLimit truncates counts as a game and gives
+    neither side points: play_match()'s rules.  epsilon: every side explores
+    with it (ply k under the tag k).  nets: 1 .. 64 value_net.ValueMLPs on the
+    env's device.  Returns league_result()'s dict with "pairs", "white" and
+    "black" (the host lists used) added."""
+    import numpy as np
+
+    from . import _lib
+
+    nets = list(nets)
+    if not 1 <= len(nets) <= _lib.LEAGUE_NETS_MAX:
+        raise ValueError(f"a league has 1 .. {_lib.LEAGUE_NETS_MAX} nets, not {len(nets)}")
+    for i, net in enumerate(nets):
+        if not (hasattr(net, "struct") and hasattr(net, "l1")):
+            raise TypeError(f"nets[{i}] must be a gym_narde.value_net.ValueMLP")
+        if net.l1.weight.device != env.device:
+            raise ValueError(f"nets[{i}] must live on the env's device")
+    if pairs is None:
+        pairs = league_pairs(len(nets), random, self_play)
+    pairs = [(int(w), int(b)) for w, b in pairs]
+    if not pairs:
+        raise ValueError("no pairs to play")
+    if any(not 0 <= x < len(nets) for p in pairs for x in p):
+        random = True  # (a given pair names the random participant)
+    B = env.num_envs
+    if B < len(pairs):
+        raise ValueError(f"{B} envs cannot hold {len(pairs)} pairs: every pair needs an env")
+    t = env.torch
+    idx = np.arange(B) % len(pairs)
+    white = np.asarray([p[0] for p in pairs], dtype=np.int32)[idx]
+    black = np.asarray([p[1] for p in pairs], dtype=np.int32)[idx]
+    table = env.net_table(nets)
+    none = dict(dice=False, value=False, reward=False, terminated=False, truncated=False)
+    none["play" if env.full else "actions"] = False
+    bufs = (env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers)(plies, **none)
+    rollout = env.turn_value_rollout_league if env.full else env.value_rollout_league
+    env.reset()
+    rollout(plies, table, t.as_tensor(white, device=env.device), t.as_tensor(black, device=env.device),
+            epsilon=epsilon, tag=None if epsilon is None else 0, seed=seed, bufs=bufs)
+    res = league_result(env.stats().cpu().numpy(), white, black, len(nets), random=random)
+    res.update(pairs=pairs, white=white, black=black)
+    return res

@@ -996,7 +996,6 @@ class VecNardeEnv:
     def _value_rollout_args(self, plies, net_white, net_black, epsilon, tag, bufs, make_bufs, layout):
         """value_rollout()'s and turn_value_rollout()'s argument checks: (plies,
         net_white, net_black, the nets' structs, epsilon, tag, bufs)."""
-        t, B = self.torch, self.num_envs
         plies = int(plies)
         if plies < 1:
             raise ValueError("plies must be >= 1")
@@ -1015,6 +1014,13 @@ class VecNardeEnv:
             if net.l1.weight.device != self.device:
                 raise ValueError("the net must live on the env's device")
             structs.append(mlp)
+        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, make_bufs, layout)
+        return plies, net_white, net_black, structs, epsilon, tag, bufs
+
+    def _value_rollout_bufs(self, plies, epsilon, tag, bufs, make_bufs, layout):
+        """The value rollouts' checks of the explore pair and the buffers (the
+        league launches' too): (epsilon, tag, bufs)."""
+        t, B = self.torch, self.num_envs
         if (epsilon is None) != (tag is None):
             raise ValueError("epsilon and tag go together")
         if epsilon is not None:
@@ -1030,7 +1036,7 @@ class VecNardeEnv:
                     or a.dim() != 2 + len(shape) or a.shape[0] < plies or tuple(a.shape[1:]) != (B,) + shape):
                 raise ValueError(f"bufs[{name!r}] must be a contiguous {dt} device tensor of shape "
                                  f"(>= {plies}, {B}{''.join(f', {k}' for k in shape)})")
-        return plies, net_white, net_black, structs, epsilon, tag, bufs
+        return epsilon, tag, bufs
 
     def value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None):
         """plies plies of value-greedy play in ONE launch, a net per colour
@@ -1142,6 +1148,116 @@ class VecNardeEnv:
                          *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
                          _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
         self._keep = (net_white, net_black, structs, epsilon, tag, bufs, scratch)
+        return bufs
+
+    def net_table(self, nets, out=None):
+        """The league launches' table of 1 .. 64 value_net.ValueMLPs on the
+        env's device (narde_net_table): a uint8 device
+        tensor of 64 bytes a net, written on the current stream by small
+        launches that carry the nets in their arguments -- no host copy, no
+        synchronise, graph-safe when out is given.  The table holds pointers,
+        not weights: after the weights change call net.pack(), as for every
+        other call, and the next launch sees them.  out: a contiguous uint8
+        device tensor of at least that size, 16-B aligned (the table is its
+        first 64 x len(nets) bytes, returned as a view).  The env keeps the
+        nets alive for as long as it lives."""
+        t = self.torch
+        nets = list(nets)
+        if not 1 <= len(nets) <= _lib.LEAGUE_NETS_MAX:
+            raise ValueError(f"a table holds 1 .. {_lib.LEAGUE_NETS_MAX} nets, not {len(nets)}")
+        structs = (_lib.ValueMlp * len(nets))()
+        for i, net in enumerate(nets):
+            if not hasattr(net, "struct"):
+                raise TypeError(f"nets[{i}] must be a gym_narde.value_net.ValueMLP")
+            if net.l1.weight.device != self.device:
+                raise ValueError(f"nets[{i}] must live on the env's device")
+            structs[i] = net.struct()
+        nbytes = _lib.league_table_bytes(len(nets))
+        if out is None:
+            out = t.empty(nbytes, dtype=t.uint8, device=self.device)
+        elif (out.dtype != t.uint8 or out.device != self.device or not out.is_contiguous() or out.dim() != 1
+              or out.numel() < nbytes or out.data_ptr() % 16):
+            raise ValueError(f"out must be a contiguous, 16-B aligned uint8 device tensor of at least {nbytes} bytes")
+        table = out[:nbytes]
+        _lib.check(self.handle.lib.narde_net_table(self.device.index, len(nets), structs, _lib.ptr(table), nbytes,
+                                                   self._s()), "narde_net_table")
+        if getattr(self, "_league_nets", None) is None:
+            self._league_nets = {}
+        self._league_nets[table.data_ptr()] = tuple(nets)
+        return table
+
+    def _league_args(self, table, white, black):
+        """The league launches' checks of the table and the two index
+        tensors: the number of nets."""
+        t, B = self.torch, self.num_envs
+        if (not isinstance(table, t.Tensor) or table.dtype != t.uint8 or table.device != self.device
+                or not table.is_contiguous() or table.dim() != 1 or table.numel() % _lib.league_table_bytes(1)
+                or not 1 <= table.numel() // _lib.league_table_bytes(1) <= _lib.LEAGUE_NETS_MAX
+                or table.data_ptr() % 16):
+            raise ValueError("table must be net_table()'s uint8 tensor on the env's device")
+        for name, a in (("white", white), ("black", black)):
+            if (not isinstance(a, t.Tensor) or a.dtype != t.int32 or a.device != self.device or not a.is_contiguous()
+                    or tuple(a.shape) != (B,)):
+                raise ValueError(f"{name} must be a contiguous int32 device tensor of shape ({B},)")
+        return table.numel() // _lib.league_table_bytes(1)
+
+    def value_rollout_league(self, plies, table, white, black, epsilon=None, tag=None, seed=0, bufs=None):
+        """value_rollout() with a net per env and colour
+        (narde_value_rollout_league): env e's white
+        plies are played under net white[e] of table (net_table()), its black
+        plies under net black[e], through every game the env plays inside the
+        launch.  white, black: (B,) int32 device tensors, read on the device;
+        an index outside the table (-1, say) makes that colour of that env
+        play the random-legal policy, bit for bit step()'s own; both colours
+        random, and white[e] == black[e], are allowed.  Env e's outputs,
+        state and stats() are bit for bit value_rollout()'s under those two
+        nets.  plies, epsilon, tag, seed, bufs (value_rollout_buffers(),
+        records=True included) and the return value are value_rollout()'s.
+        No synchronise; graph-safe under value_rollout()'s conditions, with
+        white and black rewritten in place between replays."""
+        if self.full:
+            raise ValueError('value_rollout_league() is rules="ref2" only')
+        plies = int(plies)
+        if plies < 1:
+            raise ValueError("plies must be >= 1")
+        n_nets = self._league_args(table, white, black)
+        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, self.value_rollout_buffers,
+                                                      self._VALUE_ROLLOUT_BUFS)
+        self.handle.call("narde_value_rollout_league", plies, _lib.ptr(table), n_nets, _lib.ptr(white),
+                         _lib.ptr(black), _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
+                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS),
+                         _lib.ptr(bufs.get("records")), self._s())
+        self._keep = (table, white, black, epsilon, tag, bufs)
+        return bufs
+
+    def turn_value_rollout_league(self, plies, table, white, black, epsilon=None, tag=None, seed=0, bufs=None,
+                                  scratch=None):
+        """rules="full4": turn_value_rollout() with value_rollout_league()'s
+        table, white and black (narde_turn_value_rollout_league).  bufs
+        (turn_value_rollout_buffers()) and scratch are turn_value_rollout()'s:
+        the same bits whatever the number of pieces."""
+        if not self.full:
+            raise ValueError('turn_value_rollout_league() is rules="full4" only')
+        t = self.torch
+        plies = int(plies)
+        if plies < 1:
+            raise ValueError("plies must be >= 1")
+        n_nets = self._league_args(table, white, black)
+        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, self.turn_value_rollout_buffers,
+                                                      self._TURN_VALUE_ROLLOUT_BUFS)
+        if scratch is None:
+            if getattr(self, "_turn_rollout_scratch", None) is None:
+                self._turn_rollout_scratch = self.turn_value_rollout_scratch()
+            scratch = self._turn_rollout_scratch
+        elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
+              or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
+            raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
+                             f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
+        self.handle.call("narde_turn_value_rollout_league", plies, _lib.ptr(table), n_nets, _lib.ptr(white),
+                         _lib.ptr(black), _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
+                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
+                         _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
+        self._keep = (table, white, black, epsilon, tag, bufs, scratch)
         return bufs
 
     def state_records(self, board, off, first_turn, player, t=0):

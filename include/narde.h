@@ -619,6 +619,70 @@ int narde_turn_value_rollout_records(narde_env *env, int plies, const narde_valu
                                      uint8_t *truncated, void *scratch, int64_t scratch_bytes,
                                      void *records, void *stream);
 
+/* Round-robin leagues in one launch: a value net per env and colour
+ * (DESIGN.md section 27).  The two records rollouts above with the nets taken,
+ * per env, from a table in device memory instead of from two arguments.
+ *
+ * narde_net_table writes the kernels' view of n_nets nets (a host array of
+ * narde_value_mlp) into table: device memory, 16-B aligned, table_bytes >=
+ * NARDE_LEAGUE_TABLE_BYTES(n_nets).  An entry is opaque and 64 B (the
+ * kernels' view of a net is 56 B).  The nets travel by value in the arguments
+ * of small kernel launches on the stream (16 nets a launch): no host copy, so
+ * the call is stream-ordered, allocates nothing, does not synchronise and is
+ * graph-capturable.  The weights are not copied -- an entry holds the net's
+ * pointers --, so weights changed between two launches are seen by the second,
+ * as with every other call; the nets array itself is not needed after the call
+ * returns.  Needs no handle.  NARDE_EINVAL before any device call: a negative
+ * device, NULL nets or table, n_nets outside 1..NARDE_LEAGUE_NETS_MAX, table
+ * misaligned, table_bytes too small, any net's error (narde_value_rollout's
+ * cases; the message names the net's index). */
+#define NARDE_LEAGUE_NETS_MAX 64
+#define NARDE_LEAGUE_TABLE_BYTES(n) (64 * (int64_t)(n))
+int narde_net_table(int device, int n_nets, const narde_value_mlp *nets /* host array */,
+                    void *table /* device, 16-B aligned */, int64_t table_bytes, void *stream);
+
+/* narde_value_rollout_records (REF2) except for where the nets come from: env
+ * e's white plies are played under net white[e] of the table and its black
+ * plies under net black[e], for every game the env plays inside the launch
+ * (the assignment survives auto-resets).  white, black: device i32[B], 4-B
+ * aligned, read on the device.  An index outside 0 .. n_nets - 1 (-1, n_nets,
+ * INT32_MIN, ...) makes that colour of that env play the random-legal policy,
+ * bit for bit narde_step(actions = NULL, dice = NULL, autoreset = 1), drawn
+ * from the same words of the ply stream; no table entry is read for it.  Both
+ * colours random in one env is allowed (that env plays narde_selfplay's
+ * plies), and so is white[e] == black[e] (self-play of one net).
+ * Env e's outputs, final record and statistics are, bit for bit, what
+ * narde_value_rollout_records gives env e of a handle in the same state under
+ * (nets[white[e]], nets[black[e]]) with the same epsilon, seed and tag.
+ * Stream-ordered, allocates nothing, no synchronise, graph-capturable (one
+ * kernel node: white, black, epsilon, tag and the table are read on the
+ * device).  No row or per-row value goes to memory.
+ * A table not written by narde_net_table for at least n_nets nets is the
+ * caller's error, as a bad weight pointer is: it is not detected.
+ * NARDE_EINVAL before any device call: a NULL handle, plies < 1, NULL table,
+ * white or black, table not 16-B aligned, white or black not 4-B aligned,
+ * n_nets outside 1..NARDE_LEAGUE_NETS_MAX, epsilon and tag not both set or
+ * both NULL, actions not 4-B aligned, records not 16-B aligned. */
+int narde_value_rollout_league(narde_env *env, int plies, const void *table, int n_nets,
+                               const int32_t *white, const int32_t *black, /* device i32[B] */
+                               const float *epsilon, uint64_t seed, const int64_t *tag,
+                               uint8_t *dice, int16_t *actions, float *value, int32_t *reward,
+                               uint8_t *terminated, uint8_t *truncated, void *records, void *stream);
+
+/* The same over narde_turn_value_rollout_records (FULL4): play i8[4][2] 8-B
+ * aligned, scratch and scratch_bytes with that call's piece rule.  A wave
+ * plays envs w, w + waves, ... one after another and takes each env's pair
+ * when it starts that env; the same inputs give the same bits whatever
+ * scratch_bytes.  NARDE_EINVAL: narde_value_rollout_league's cases with play
+ * not 8-B aligned in place of actions, a NULL or misaligned scratch,
+ * scratch_bytes below one piece. */
+int narde_turn_value_rollout_league(narde_env *env, int plies, const void *table, int n_nets,
+                                    const int32_t *white, const int32_t *black,
+                                    const float *epsilon, uint64_t seed, const int64_t *tag,
+                                    uint8_t *dice, int8_t *play, float *value, int32_t *reward,
+                                    uint8_t *terminated, uint8_t *truncated, void *scratch,
+                                    int64_t scratch_bytes, void *records, void *stream);
+
 /* Monte-Carlo playouts: given positions played to the end under value nets
  * (DESIGN.md section 22).
  *
