@@ -28,6 +28,10 @@ namespace {
 //   the auto-reset) and stores the ply's outputs from lane 0.
 // No row, feature or per-row value goes to memory.  The env-to-wave
 // assignment is static: nothing spins and nothing is claimed with an atomic.
+// The ply is tvr_ply below: k_turn_value_rollout_league (kernels_league.h)
+// runs it through tvr_env_plies, k_turn_value_playout
+// (kernels_turn_value_playout.h) in its own loop; k_turn_value_rollout, at the
+// end of this file, still spells the same ply out (the reason is there).
 static_assert(NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) == (int64_t)kTurnSlabWave, "narde.h states the same slab piece");
 
 struct TvrArgs {
@@ -109,8 +113,114 @@ __device__ __forceinline__ int turn_pick_roll(TurnPick& pk, uint64_t* knxt, uint
                                                    &pk);
 }
 
+// wave `wave`'s piece of the caller's slab: a level's keys and its two path arrays
+struct TurnSlab {
+  uint64_t* key;
+  uint32_t* pathA;
+  uint32_t* pathB;
+};
+__device__ __forceinline__ TurnSlab turn_slab(uint8_t* slab, int wave) {
+  uint64_t* const key = reinterpret_cast<uint64_t*>(slab + (size_t)wave * kTurnSlabWave);
+  uint32_t* const pathA = reinterpret_cast<uint32_t*>(key + kTurnSlabKeys);
+  return TurnSlab{key, pathA, pathA + kTurnAftMax};
+}
+
+// what a ply leaves for its caller besides the record it advanced
+struct TvrPly {
+  int d0, d1;
+  bool black;     // the mover
+  RowBest b;      // the row played (ord < 0: none)
+  uint64_t play;  // the turn played: the row's play word, or the random-legal turn's
+  TurnOut o;
+  int term, trunc;
+};
+
+// Ply k of env index e's stream on s: the one FULL4 ply of the rollout, league
+// and playout kernels (vr_ply's arguments, with the frontier in LDS and the
+// wave's slab piece in place of the REF2 expansion's blocks).  All lanes of the
+// wave call it with the same arguments.
+template <bool kStats, class Nets>
+__device__ __forceinline__ TvrPly tvr_ply(Side& s, const Rng& g, int e, int k, const Nets& nets, const VrExplore& ex,
+                                          int max_steps, bool auto_reset, const TurnSlab& slab, TurnFrontLds& F,
+                                          TurnScan& L, ValStage& VS, VrCarry& C, int lane) {
+  TvrPly p;
+  {
+    uint32_t R[4], r[4];
+    if (k > 0) vr_load4(C.R, R);
+    ply_draw_cached(g, s.t, (uint32_t)e, R, k == 0, r);
+    if (lane == 0) C.R = make_uint4(R[0], R[1], R[2], R[3]);
+    dice_from(r[0], g.dice_mode, p.d0, p.d1);
+    p.d0 = (int)vr_uniform((uint32_t)p.d0);
+    p.d1 = (int)vr_uniform((uint32_t)p.d1);
+  }
+  p.black = vr_uniform(s.black) != 0u;
+  const bool has = nets.has(p.black);
+  p.b = row_best_none();
+  uint64_t pw = ~0ull;  // no row: the all -1 play
+  if (has) {            // wave-uniform
+    const ValNet vn = nets.net(p.black);
+    uint32_t r1 = 0u;
+    const bool explore = ex.on && explore_draw(ex.tag0 + (uint32_t)k, (uint32_t)e, ex.k0, ex.k1, ex.eps_q32, r1);
+    // the values are white's: black plays the smallest
+    TurnPick pk{{s, p.d0, p.d1, nullptr, p.black, 0.0f}, vr_uniform(explore ? 1u : 0u) != 0u, vr_uniform(r1),
+                row_best_none(), 0, 0, 0};
+    wave_lds_handoff();  // the last ply's reads of the frontier are done
+    int nrows = turn_pick_roll(pk, F.key, F.path[0], F.path[1], kTurnFront, L, vn, VS);
+    if (nrows < 0) {  // wave-uniform: the same walk in the wave's piece of the slab
+      wave_lds_handoff();
+      nrows = turn_pick_roll(pk, slab.key, slab.pathA, slab.pathB, kTurnAftMax, L, vn, VS);
+    }
+    // (kTurnAftMax bounds every level: nrows < 0 cannot happen twice; it would be a pass)
+    if (nrows > 0) {
+      p.b = pk.b;
+      pw = turn_path_play_words(p.b.codes, pk.level, pk.dh, pk.dl);
+    }
+  }
+  wave_lds_handoff();  // lane 0's block and increments, to every lane
+  uint32_t R[4], r[4];
+  vr_load4(C.R, R);
+  ply_words_of(R, s.t, g.dice_mode, r);
+  int4 st = make_int4(0, 0, 0, 0);
+  if (kStats) st = C.st;
+  if (has)  // wave-uniform
+    env_ply_full(s, st, r, g.env0 + (uint32_t)e, g.k0, g.k1, false, 0, 0, g.dice_mode, true, pw, max_steps, auto_reset,
+                 p.o, p.term, p.trunc);
+  else  // narde_step_full(play = NULL)'s own turn (every lane the same env: its cooperative passes find 64 equal owners)
+    ply_full_words(s, st, r, g.dice_mode, max_steps, auto_reset, p.o, p.term, p.trunc);
+  p.play = has ? pw : p.o.played;
+  wave_lds_handoff();  // (every lane has read the block and the increments)
+  if (kStats && lane == 0) C.st = st;
+  return p;
+}
+
+// env e's plies of a launch (vr_env_plies, whole turns); a wave plays several
+// envs, one after the other
+template <bool kRec, class Nets>
+__device__ __forceinline__ void tvr_env_plies(const TvrArgs& a, int e, const Nets& nets, const TurnSlab& slab,
+                                              TurnFrontLds& F, TurnScan& L, ValStage& VS, VrCarry& C, int lane) {
+  Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
+  const VrExplore ex = vr_explore(a.eps, a.tag, a.k0, a.k1);
+  wave_lds_handoff();  // (the last env's reads of the carry are done)
+  if (lane == 0) C.st = make_int4(0, 0, 0, 0);
+  for (int k = 0; k < a.plies; ++k) {
+    const size_t ix = (size_t)k * (size_t)a.n + (size_t)e;
+    if (kRec && lane == 0) vr_store_record(a.records, ix, s);
+    const TvrPly p = tvr_ply<true>(s, a.g, e, k, nets, ex, a.max_steps, true, slab, F, L, VS, C, lane);
+    if (lane == 0) {
+      if (a.play) a.play[ix] = p.play;
+      vr_store_ply(a, ix, p);
+    }
+  }
+  if (lane == 0) vr_finish(a.pl, e, s, C);
+}
+
 // one-wave workgroups; wave w plays envs w, w + gridDim.x, ... (the LDS of
-// k_turn_look<1> and the carry); kRec: a.records is written (vr_store_record)
+// k_turn_look<1> and the carry); kRec: a.records is written (vr_store_record).
+// The one kernel that keeps its own text of tvr_env_plies and tvr_ply: over
+// them it measured 0.2 to 1.0 % slower than this body, outside the runs' spread
+// at B = 65,536 ("Tried"); the league and playout
+// kernels did not.  A change to tvr_ply is made here too;
+// tests/test_gpu_league.py holds the two equal byte for byte.
 template <bool kRec>
 __global__ void __launch_bounds__(64) k_turn_value_rollout(TvrArgs a, ValNet net_w, ValNet net_b, int has_w,
                                                            int has_b) {

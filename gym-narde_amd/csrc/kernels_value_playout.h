@@ -1,8 +1,8 @@
 // kernels_value_playout.h -- Monte-Carlo playouts of given positions under value nets
 // Part of the one translation unit narde.hip (included there, in order,
 // behind kernels_value_rollout.h and kernels_turn_value_rollout.h: the ply is
-// k_value_rollout's, vr_choose, vr_net, vr_uniform and the carry are there);
-// not a standalone header.
+// vr_ply there, as are vr_net, vr_uniform and the carry); not a standalone
+// header.
 #pragma once
 
 namespace {
@@ -100,38 +100,13 @@ __global__ void __launch_bounds__(64) k_value_playout(VpArgs a, ValNet net_w, Va
   const int e = a.common ? q - root * a.trials : q;  // the trial's env index in the ply stream
   Side s = side_from_record(a.roots[2 * (size_t)root], a.roots[2 * (size_t)root + 1]);
   int done = 0, outc = 0, len = 0;
-  for (int k = 0; k < a.max_plies; ++k) {
-    int d0, d1;
-    {
-      uint32_t R[4], r[4];
-      if (k > 0) vr_load4(C.R, R);
-      ply_draw_cached(a.g, s.t, (uint32_t)e, R, k == 0, r);
-      if (lane == 0) C.R = make_uint4(R[0], R[1], R[2], R[3]);
-      dice_from(r[0], a.g.dice_mode, d0, d1);
-      d0 = (int)vr_uniform((uint32_t)d0);
-      d1 = (int)vr_uniform((uint32_t)d1);
-    }
-    const bool black = vr_uniform(s.black) != 0u;
-    const bool has = (black ? has_b : has_w) != 0;
-    RowBest b = row_best_none();
-    if (has) {  // wave-uniform
-      const ValNet vn = vr_net(black, net_w, net_b);
-      b = vr_choose(s, d0, d1, vn, L, VS, CS, lane, false, 0u);
-    }
-    const int c1 = (int)(int16_t)(b.codes & 0xFFFFu), c2 = (int)(int16_t)(b.codes >> 16);  // (no row: 0, 0)
-    wave_lds_handoff();  // lane 0's block, to every lane
-    uint32_t R[4], r[4];
-    vr_load4(C.R, R);
-    ply_words_of(R, s.t, a.g.dice_mode, r);
-    int4 st = make_int4(0, 0, 0, 0);
-    StepOut o;
-    int term, trunc;
-    env_ply(s, st, r, false, 0, 0, a.g.dice_mode, !has, c1, c2, 0, false, o, term, trunc);
-    wave_lds_handoff();  // (every lane has read the block)
+  const VrTwoNets nets{net_w, net_b, has_w, has_b};
+  for (int k = 0; k < a.max_plies; ++k) {  // greedy plies, max_steps 0, no auto-reset, no statistics
+    const VrPly p = vr_ply<false>(s, a.g, e, k, nets, VrExplore{}, 0, false, L, VS, CS, C, lane);
     len = k + 1;
-    if (vr_uniform((uint32_t)term) != 0u) {  // wave-uniform: the trial ends here
+    if (vr_uniform((uint32_t)p.term) != 0u) {  // wave-uniform: the trial ends here
       done = 1;
-      outc = (int)vr_uniform((uint32_t)(black ? -o.reward : o.reward));
+      outc = (int)vr_uniform((uint32_t)(p.black ? -p.o.reward : p.o.reward));
       break;
     }
   }

@@ -29,6 +29,10 @@ namespace {
 // No row, feature or per-row value goes to memory.  An env is one wave
 // whatever B: splitting an env's chunks over several waves for tiny B is not
 // done (section 19.5).
+// The ply is vr_ply below, the one REF2 ply: k_value_rollout and
+// k_value_rollout_league (kernels_league.h) run it through vr_env_plies,
+// k_value_playout (kernels_value_playout.h) in its own loop.  vr_store_ply and
+// vr_finish are the FULL4 loop's too.
 struct VrArgs {
   Planes pl;
   int n;
@@ -149,74 +153,131 @@ __device__ __forceinline__ void vr_store_record(uint4* __restrict__ records, siz
   records[2 * ix + 1] = rb;
 }
 
-// one wave per env, an env per workgroup (k_aft_look<1>'s LDS and the codes);
-// kRec: a.records is written (the no-records instantiation holds no trace of it)
+// the explore draws' parameters of a launch (on = false: every ply is greedy)
+struct VrExplore {
+  bool on;
+  uint64_t eps_q32;
+  uint32_t tag0, k0, k1;  // ply k's tag is tag0 + k; the draws' key
+};
+__device__ __forceinline__ VrExplore vr_explore(const float* eps, const int64_t* tag, uint32_t k0, uint32_t k1) {
+  return VrExplore{eps != nullptr, eps ? eps_to_q32(*eps) : 0ull, eps ? (uint32_t)*tag : 0u, k0, k1};
+}
+
+// Where the mover's net comes from: has(black) says whether that colour has a
+// net (wave-uniform; none: the random-legal policy), net(black) gives it with
+// every field a scalar.  The launch's two nets here; the league's table entry
+// of the env's pair in kernels_league.h (LeagueNets).
+struct VrTwoNets {
+  const ValNet& w;
+  const ValNet& b;
+  int has_w, has_b;
+  __device__ __forceinline__ bool has(bool black) const { return (black ? has_b : has_w) != 0; }
+  __device__ __forceinline__ ValNet net(bool black) const { return vr_net(black, w, b); }
+};
+
+// what a ply leaves for its caller besides the record it advanced
+struct VrPly {
+  int d0, d1;
+  bool black;  // the mover
+  RowBest b;   // the row played (ord < 0: none)
+  StepOut o;
+  int term, trunc;
+};
+
+// Ply k of env index e's stream on s: the one REF2 ply of the rollout, league
+// and playout kernels.  kStats: the statistics increments are carried in C.st
+// across the plies (the caller zeroes it before ply 0); otherwise they are
+// dropped.  All lanes of the wave call it with the same arguments.
+template <bool kStats, class Nets>
+__device__ __forceinline__ VrPly vr_ply(Side& s, const Rng& g, int e, int k, const Nets& nets, const VrExplore& ex,
+                                        int max_steps, bool auto_reset, AftScan& L, ValStage& VS, VrStage& CS,
+                                        VrCarry& C, int lane) {
+  VrPly p;
+  {
+    uint32_t R[4], r[4];
+    if (k > 0) vr_load4(C.R, R);
+    ply_draw_cached(g, s.t, (uint32_t)e, R, k == 0, r);
+    if (lane == 0) C.R = make_uint4(R[0], R[1], R[2], R[3]);
+    dice_from(r[0], g.dice_mode, p.d0, p.d1);
+    p.d0 = (int)vr_uniform((uint32_t)p.d0);
+    p.d1 = (int)vr_uniform((uint32_t)p.d1);
+  }
+  p.black = vr_uniform(s.black) != 0u;
+  const bool has = nets.has(p.black);
+  p.b = row_best_none();
+  if (has) {  // wave-uniform
+    const ValNet vn = nets.net(p.black);
+    uint32_t r1 = 0u;
+    const bool explore = ex.on && explore_draw(ex.tag0 + (uint32_t)k, (uint32_t)e, ex.k0, ex.k1, ex.eps_q32, r1);
+    p.b = vr_choose(s, p.d0, p.d1, vn, L, VS, CS, lane, vr_uniform(explore ? 1u : 0u) != 0u, vr_uniform(r1));
+  }
+  const int c1 = (int)(int16_t)(p.b.codes & 0xFFFFu), c2 = (int)(int16_t)(p.b.codes >> 16);  // (no row: 0, 0)
+  wave_lds_handoff();  // lane 0's block and increments, to every lane
+  uint32_t R[4], r[4];
+  vr_load4(C.R, R);
+  ply_words_of(R, s.t, g.dice_mode, r);
+  int4 st = make_int4(0, 0, 0, 0);
+  if (kStats) st = C.st;
+  env_ply(s, st, r, false, 0, 0, g.dice_mode, !has, c1, c2, max_steps, auto_reset, p.o, p.term, p.trunc);
+  wave_lds_handoff();  // (every lane has read the block and the increments)
+  if (kStats && lane == 0) C.st = st;
+  return p;
+}
+
+// ply k's outputs of env e that both rule sets have, from lane 0 (the action
+// or play column is the caller's): Args is VrArgs or TvrArgs, Ply VrPly or TvrPly
+template <class Args, class Ply>
+__device__ __forceinline__ void vr_store_ply(const Args& a, size_t ix, const Ply& p) {
+  if (a.dice) {
+    a.dice[2 * ix] = (uint8_t)p.d0;
+    a.dice[2 * ix + 1] = (uint8_t)p.d1;
+  }
+  if (a.value) a.value[ix] = p.b.ord >= 0 ? p.b.v : __builtin_nanf("");
+  if (a.reward) a.reward[ix] = p.o.reward;
+  if (a.term) a.term[ix] = (uint8_t)p.term;
+  if (a.trunc) a.trunc[ix] = (uint8_t)p.trunc;
+}
+
+// the end of env e's plies, from lane 0: the record back to the planes and the
+// carried increments (lane 0's own last write) to the statistics
+__device__ __forceinline__ void vr_finish(const Planes& pl, int e, const Side& s, const VrCarry& C) {
+  uint4 ra, rb;
+  side_to_record(s, ra, rb);
+  pl.p0[e] = ra;
+  pl.p1[e] = rb;
+  add_stats(pl.stats, e, C.st);
+}
+
+// env e's plies of a launch: the record stays in registers across them; kRec:
+// a.records is written (the no-records instantiations hold no trace of it)
+template <bool kRec, class Nets>
+__device__ __forceinline__ void vr_env_plies(const VrArgs& a, int e, const Nets& nets, AftScan& L, ValStage& VS,
+                                             VrStage& CS, VrCarry& C, int lane) {
+  Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
+  const VrExplore ex = vr_explore(a.eps, a.tag, a.k0, a.k1);
+  if (lane == 0) C.st = make_int4(0, 0, 0, 0);
+  for (int k = 0; k < a.plies; ++k) {
+    const size_t ix = (size_t)k * (size_t)a.n + (size_t)e;
+    if (kRec && lane == 0) vr_store_record(a.records, ix, s);
+    const VrPly p = vr_ply<true>(s, a.g, e, k, nets, ex, a.max_steps, true, L, VS, CS, C, lane);
+    if (lane == 0) {
+      if (a.actions) reinterpret_cast<uint32_t*>(a.actions)[ix] = pack_codes(p.o.code1, p.o.code2);
+      vr_store_ply(a, ix, p);
+    }
+  }
+  if (lane == 0) vr_finish(a.pl, e, s, C);
+}
+
+// one wave per env, an env per workgroup (k_aft_look<1>'s LDS and the codes)
 template <bool kRec>
 __global__ void __launch_bounds__(64) k_value_rollout(VrArgs a, ValNet net_w, ValNet net_b, int has_w, int has_b) {
   __shared__ AftScan L;
   __shared__ ValStage VS;
   __shared__ VrStage CS;
   __shared__ VrCarry C;
-  const int lane = threadIdx.x & 63;
   const int e = __builtin_amdgcn_readfirstlane((int)blockIdx.x);
   if (e >= a.n) return;
-  Side s = side_from_record(a.pl.p0[e], a.pl.p1[e]);
-  const uint64_t eps_q32 = a.eps ? eps_to_q32(*a.eps) : 0ull;
-  const uint32_t tag0 = a.eps ? (uint32_t)*a.tag : 0u;
-  if (lane == 0) C.st = make_int4(0, 0, 0, 0);
-  for (int k = 0; k < a.plies; ++k) {
-    if (kRec && lane == 0) vr_store_record(a.records, (size_t)k * (size_t)a.n + (size_t)e, s);
-    int d0, d1;
-    {
-      uint32_t R[4], r[4];
-      if (k > 0) vr_load4(C.R, R);
-      ply_draw_cached(a.g, s.t, (uint32_t)e, R, k == 0, r);
-      if (lane == 0) C.R = make_uint4(R[0], R[1], R[2], R[3]);
-      dice_from(r[0], a.g.dice_mode, d0, d1);
-      d0 = (int)vr_uniform((uint32_t)d0);
-      d1 = (int)vr_uniform((uint32_t)d1);
-    }
-    const bool black = vr_uniform(s.black) != 0u;
-    const bool has = (black ? has_b : has_w) != 0;
-    RowBest b = row_best_none();
-    if (has) {  // wave-uniform
-      const ValNet vn = vr_net(black, net_w, net_b);
-      uint32_t r1 = 0u;
-      const bool explore = a.eps && explore_draw(tag0 + (uint32_t)k, (uint32_t)e, a.k0, a.k1, eps_q32, r1);
-      b = vr_choose(s, d0, d1, vn, L, VS, CS, lane, vr_uniform(explore ? 1u : 0u) != 0u, vr_uniform(r1));
-    }
-    const int c1 = (int)(int16_t)(b.codes & 0xFFFFu), c2 = (int)(int16_t)(b.codes >> 16);  // (no row: 0, 0)
-    wave_lds_handoff();  // lane 0's block and increments, to every lane
-    uint32_t R[4], r[4];
-    vr_load4(C.R, R);
-    ply_words_of(R, s.t, a.g.dice_mode, r);
-    const int4 st0 = C.st;
-    int4 st = st0;
-    StepOut o;
-    int term, trunc;
-    env_ply(s, st, r, false, 0, 0, a.g.dice_mode, !has, c1, c2, a.max_steps, true, o, term, trunc);
-    wave_lds_handoff();  // (every lane has read the increments)
-    if (lane == 0) {
-      C.st = st;
-      const size_t ix = (size_t)k * (size_t)a.n + (size_t)e;
-      if (a.dice) {
-        a.dice[2 * ix] = (uint8_t)d0;
-        a.dice[2 * ix + 1] = (uint8_t)d1;
-      }
-      if (a.actions) reinterpret_cast<uint32_t*>(a.actions)[ix] = pack_codes(o.code1, o.code2);
-      if (a.value) a.value[ix] = b.ord >= 0 ? b.v : __builtin_nanf("");
-      if (a.reward) a.reward[ix] = o.reward;
-      if (a.term) a.term[ix] = (uint8_t)term;
-      if (a.trunc) a.trunc[ix] = (uint8_t)trunc;
-    }
-  }
-  if (lane == 0) {
-    uint4 ra, rb;
-    side_to_record(s, ra, rb);
-    a.pl.p0[e] = ra;
-    a.pl.p1[e] = rb;
-    add_stats(a.pl.stats, e, C.st);  // (lane 0's own last write)
-  }
+  vr_env_plies<kRec>(a, e, VrTwoNets{net_w, net_b, has_w, has_b}, L, VS, CS, C, threadIdx.x & 63);
 }
 
 }  // namespace

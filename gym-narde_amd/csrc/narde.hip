@@ -436,6 +436,15 @@ int check_records_lookahead(const narde_env* e, int64_t n, const void* records, 
   return check_value_net(net, 1, value, vn);
 }
 
+// a value or league rollout kernel's launch, `waves` one-wave workgroups: its
+// <true> instantiation if the call has a records column, else its <false> one
+template <class... P, class... A>
+int launch_rollout(bool records, void (*with)(P...), void (*without)(P...), int64_t waves, void* stream,
+                   const char* what, const A&... args) {
+  (records ? with : without)<<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(args...);
+  return check_launch(what);
+}
+
 }  // namespace
 
 extern "C" {
@@ -912,24 +921,64 @@ int narde_afterstate_pick(narde_env* e, const int32_t* offsets, const int16_t* c
 
 namespace {
 
-// The value rollouts' (narde_value_rollout, narde_turn_value_rollout) checks of
-// the plies, the explore pair, the action column (`align`-byte words;
-// misaligned: the error's text) and the two nets, and the kernels' view of the
-// nets (the kernels store no per-row value: a net's value pointer stays NULL)
+// What the value rollouts and the league rollouts check alike, in two parts
+// (each call's own checks go between them): the handle and the plies; the
+// explore pair and the action column (`align`-byte words; misaligned: the
+// error's text)
+int check_rollout_handle(const narde_env* e, int plies) {
+  if (!e) return fail(NARDE_EINVAL, "NULL handle");
+  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  return NARDE_OK;
+}
+int check_rollout_columns(const float* epsilon, const int64_t* tag, const void* column, unsigned align,
+                          const char* misaligned) {
+  if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
+  if (reinterpret_cast<uintptr_t>(column) % align) return fail(NARDE_EINVAL, "%s", misaligned);
+  return NARDE_OK;
+}
+
+// The value rollouts' (narde_value_rollout, narde_turn_value_rollout) checks,
+// and the kernels' view of the two nets (the kernels store no per-row value: a
+// net's value pointer stays NULL)
 int check_rollout_nets(const narde_env* e, int plies, const narde_value_mlp* net_white,
                        const narde_value_mlp* net_black, const float* epsilon, const int64_t* tag, const void* column,
                        unsigned align, const char* misaligned, ValNet& vw, ValNet& vb) {
-  if (!e) return fail(NARDE_EINVAL, "NULL handle");
-  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  if (const int rc = check_rollout_handle(e, plies)) return rc;
   if (!net_white && !net_black)
     return fail(NARDE_EINVAL, "no net for either colour: random play against itself is narde_selfplay");
-  if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
-  if (reinterpret_cast<uintptr_t>(column) % align) return fail(NARDE_EINVAL, "%s", misaligned);
+  if (const int rc = check_rollout_columns(epsilon, tag, column, align, misaligned)) return rc;
   if (net_white)
     if (const int rc = check_value_mlp(net_white, 1, nullptr, kValLdMax, vw)) return rc;
   if (net_black)
     if (const int rc = check_value_mlp(net_black, 1, nullptr, kValLdMax, vb)) return rc;
   return NARDE_OK;
+}
+
+// The FULL4 rollouts' and playout's slab: how many waves' pieces it holds
+int check_turn_scratch(const void* scratch, int64_t scratch_bytes, int64_t& pieces) {
+  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
+  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
+  pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
+  if (pieces < 1)
+    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
+                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  return NARDE_OK;
+}
+
+// the rollout kernels' arguments of a call (two-net and league alike)
+VrArgs vr_args(const narde_env* e, int plies, const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice,
+               int16_t* actions, float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated,
+               void* records) {
+  return VrArgs{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
+                (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated,
+                (uint4*)records};
+}
+TvrArgs tvr_args(const narde_env* e, int plies, const float* epsilon, uint64_t seed, const int64_t* tag, uint8_t* dice,
+                 int8_t* play, float* value, int32_t* reward, uint8_t* terminated, uint8_t* truncated, void* scratch,
+                 void* records) {
+  return TvrArgs{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
+                 (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
+                 truncated, (uint8_t*)scratch, (uint4*)records};
 }
 
 }  // namespace
@@ -944,16 +993,9 @@ int narde_value_rollout_records(narde_env* e, int plies, const narde_value_mlp* 
     return rc;
   if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
-  const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
-                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated,
-                 (uint4*)records};
-  if (records)
-    k_value_rollout<true><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                           net_black != nullptr);
-  else
-    k_value_rollout<false><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                            net_black != nullptr);
-  return check_launch("k_value_rollout");
+  const VrArgs a = vr_args(e, plies, epsilon, seed, tag, dice, actions, value, reward, terminated, truncated, records);
+  return launch_rollout(records != nullptr, k_value_rollout<true>, k_value_rollout<false>, e->n, stream,
+                        "k_value_rollout", a, vw, vb, (int)(net_white != nullptr), (int)(net_black != nullptr));
 }
 
 int narde_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white, const narde_value_mlp* net_black,
@@ -985,25 +1027,15 @@ int narde_turn_value_rollout_records(narde_env* e, int plies, const narde_value_
   if (const int rc = check_rollout_nets(e, plies, net_white, net_black, epsilon, tag, play, 8,
                                         "play must be 8-B aligned", vw, vb))
     return rc;
-  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
-  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
-  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
-  if (pieces < 1)
-    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
-                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  int64_t pieces;
+  if (const int rc = check_turn_scratch(scratch, scratch_bytes, pieces)) return rc;
   if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
-  const int64_t waves = pieces < e->n ? pieces : e->n;
-  const TvrArgs a{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
-                  (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
-                  truncated, (uint8_t*)scratch, (uint4*)records};
-  if (records)
-    k_turn_value_rollout<true><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                                 net_black != nullptr);
-  else
-    k_turn_value_rollout<false><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, vw, vb, net_white != nullptr,
-                                                                                  net_black != nullptr);
-  return check_launch("k_turn_value_rollout");
+  const TvrArgs a =
+      tvr_args(e, plies, epsilon, seed, tag, dice, play, value, reward, terminated, truncated, scratch, records);
+  return launch_rollout(records != nullptr, k_turn_value_rollout<true>, k_turn_value_rollout<false>,
+                        pieces < e->n ? pieces : e->n, stream, "k_turn_value_rollout", a, vw, vb,
+                        (int)(net_white != nullptr), (int)(net_black != nullptr));
 }
 
 int narde_turn_value_rollout(narde_env* e, int plies, const narde_value_mlp* net_white,
@@ -1057,17 +1089,14 @@ namespace {
 int check_league(const narde_env* e, int plies, const void* table, int n_nets, const int32_t* white,
                  const int32_t* black, const float* epsilon, const int64_t* tag, const void* column, unsigned align,
                  const char* misaligned) {
-  if (!e) return fail(NARDE_EINVAL, "NULL handle");
-  if (plies < 1) return fail(NARDE_EINVAL, "plies %d below 1", plies);
+  if (const int rc = check_rollout_handle(e, plies)) return rc;
   if (!table || !white || !black) return fail(NARDE_EINVAL, "NULL argument");
   if (!aligned16(table)) return fail(NARDE_EINVAL, "table must be 16-B aligned");
   if ((reinterpret_cast<uintptr_t>(white) | reinterpret_cast<uintptr_t>(black)) & 3u)
     return fail(NARDE_EINVAL, "white and black must be 4-B aligned");
   if (n_nets < 1 || n_nets > NARDE_LEAGUE_NETS_MAX)
     return fail(NARDE_EINVAL, "n_nets %d outside 1..%d", n_nets, NARDE_LEAGUE_NETS_MAX);
-  if ((epsilon != nullptr) != (tag != nullptr)) return fail(NARDE_EINVAL, "epsilon and tag go together");
-  if (reinterpret_cast<uintptr_t>(column) % align) return fail(NARDE_EINVAL, "%s", misaligned);
-  return NARDE_OK;
+  return check_rollout_columns(epsilon, tag, column, align, misaligned);
 }
 
 }  // namespace
@@ -1081,15 +1110,10 @@ int narde_value_rollout_league(narde_env* e, int plies, const void* table, int n
     return rc;
   if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
-  const VrArgs a{e->pl,  (int)e->n,        rng_of(e), e->max_steps, plies,  epsilon,    tag,      (uint32_t)seed,
-                 (uint32_t)(seed >> 32), dice,      actions,      value,  reward,     terminated, truncated,
-                 (uint4*)records};
+  const VrArgs a = vr_args(e, plies, epsilon, seed, tag, dice, actions, value, reward, terminated, truncated, records);
   const LeagueArgs lg{static_cast<const LeagueNet*>(table), n_nets, white, black};
-  if (records)
-    k_value_rollout_league<true><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, lg);
-  else
-    k_value_rollout_league<false><<<(unsigned)e->n, 64, 0, (hipStream_t)stream>>>(a, lg);
-  return check_launch("k_value_rollout_league");
+  return launch_rollout(records != nullptr, k_value_rollout_league<true>, k_value_rollout_league<false>, e->n, stream,
+                        "k_value_rollout_league", a, lg);
 }
 
 int narde_turn_value_rollout_league(narde_env* e, int plies, const void* table, int n_nets, const int32_t* white,
@@ -1100,24 +1124,15 @@ int narde_turn_value_rollout_league(narde_env* e, int plies, const void* table, 
   if (const int rc = check_league(e, plies, table, n_nets, white, black, epsilon, tag, play, 8,
                                   "play must be 8-B aligned"))
     return rc;
-  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
-  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
-  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
-  if (pieces < 1)
-    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
-                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  int64_t pieces;
+  if (const int rc = check_turn_scratch(scratch, scratch_bytes, pieces)) return rc;
   if (!aligned16(records)) return fail(NARDE_EINVAL, "records must be 16-B aligned");
   DeviceGuard dg(e->device);
-  const int64_t waves = pieces < e->n ? pieces : e->n;
-  const TvrArgs a{e->pl,      (int)e->n, rng_of(e), e->max_steps, plies,      epsilon,   tag, (uint32_t)seed,
-                  (uint32_t)(seed >> 32), dice, reinterpret_cast<uint64_t*>(play), value, reward, terminated,
-                  truncated, (uint8_t*)scratch, (uint4*)records};
+  const TvrArgs a =
+      tvr_args(e, plies, epsilon, seed, tag, dice, play, value, reward, terminated, truncated, scratch, records);
   const LeagueArgs lg{static_cast<const LeagueNet*>(table), n_nets, white, black};
-  if (records)
-    k_turn_value_rollout_league<true><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, lg);
-  else
-    k_turn_value_rollout_league<false><<<(unsigned)waves, 64, 0, (hipStream_t)stream>>>(a, lg);
-  return check_launch("k_turn_value_rollout_league");
+  return launch_rollout(records != nullptr, k_turn_value_rollout_league<true>, k_turn_value_rollout_league<false>,
+                        pieces < e->n ? pieces : e->n, stream, "k_turn_value_rollout_league", a, lg);
 }
 
 int narde_state_records(int device, int64_t n, const int8_t* board, const uint8_t* off, const uint8_t* first_turn,
@@ -1206,12 +1221,8 @@ int narde_turn_value_playout(narde_env* e, int64_t n, const void* roots, int tri
   if (const int rc = check_playout(e, n, roots, trials, max_plies, net_white, net_black, seed, id_base, flags, sums,
                                    outcome, length, leaf, a, vw, vb))
     return rc;
-  if (!scratch) return fail(NARDE_EINVAL, "NULL scratch");
-  if (!aligned16(scratch)) return fail(NARDE_EINVAL, "scratch must be 16-B aligned");
-  const int64_t pieces = scratch_bytes < 0 ? 0 : scratch_bytes / NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1);
-  if (pieces < 1)
-    return fail(NARDE_EINVAL, "scratch_bytes %lld below one wave's piece, NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1) = %lld",
-                (long long)scratch_bytes, (long long)NARDE_TURN_ROLLOUT_SCRATCH_BYTES(1));
+  int64_t pieces;
+  if (const int rc = check_turn_scratch(scratch, scratch_bytes, pieces)) return rc;
   DeviceGuard dg(e->device);
   const int64_t total = n * trials;
   const int64_t waves = pieces < total ? pieces : total;

@@ -22,6 +22,7 @@ import pytest
 from conftest import ROOT
 from test_value_cpu import make_net
 from test_value_rollout_cpu import endgames
+from turn_afterstates_ref import BIG_ROWS, big_state
 
 pytestmark = pytest.mark.gpu
 
@@ -33,6 +34,7 @@ WHO = (0, 1, 2, 3, -1)
 PAIRS25 = [(w, b) for w in WHO for b in WHO]  # (i, i) and (-1, -1) among them
 RULES = ("ref2", "full4")
 INT32_MIN = -(2 ** 31)
+BIG_SEED = 20251022  # envs 2, 24, 29 and 34 of 64 roll 1-1 first
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -50,10 +52,10 @@ def np_(x):
     return x.detach().cpu().numpy()
 
 
-def make_env(B, max_steps=1000, state=None, rules="ref2"):
+def make_env(B, max_steps=1000, state=None, rules="ref2", seed=SEED):
     from gym_narde.vector import VecNardeEnv
 
-    env = VecNardeEnv(B, device="cuda:0", seed=SEED, env_id_offset=ENV0, max_episode_steps=max_steps, rules=rules)
+    env = VecNardeEnv(B, device="cuda:0", seed=seed, env_id_offset=ENV0, max_episode_steps=max_steps, rules=rules)
     if state is not None:
         env.set_state(*(torch.as_tensor(a).to(env.device) for a in state))
     return env
@@ -131,7 +133,8 @@ def norm(i, n):
     return i if 0 <= i < n else -1
 
 
-def check_against_two_net(rules, B, plies, nets, white, black, got, env, max_steps=1000, state=None, what="", **kw):
+def check_against_two_net(rules, B, plies, nets, white, black, got, env, max_steps=1000, state=None, what="",
+                          env_seed=SEED, **kw):
     """Every env of `env` (after the league launch that gave `got`) against
     the two-net reference of its pair.  Returns {pair: compared plies}."""
     n = len(nets)
@@ -142,7 +145,7 @@ def check_against_two_net(rules, B, plies, nets, white, black, got, env, max_ste
         pairs.setdefault((norm(white[e], n), norm(black[e], n)), []).append(e)
     counts = {}
     for (i, j), envs in sorted(pairs.items()):
-        ref = make_env(B, max_steps, state, rules)
+        ref = make_env(B, max_steps, state, rules, env_seed)
         if i < 0 and j < 0:
             want = random_loop(ref, plies)
         else:
@@ -162,15 +165,16 @@ def check_against_two_net(rules, B, plies, nets, white, black, got, env, max_ste
     return counts
 
 
-def run_case(rules, B, plies, nets, pairs=PAIRS25, max_steps=1000, state=None, scratch_pieces=None, what="", **kw):
-    env = make_env(B, max_steps, state, rules)
+def run_case(rules, B, plies, nets, pairs=PAIRS25, max_steps=1000, state=None, scratch_pieces=None, what="",
+             env_seed=SEED, **kw):
+    env = make_env(B, max_steps, state, rules, env_seed)
     table = env.net_table(nets)
     white, black = cycle(pairs, B)
     extra = dict(kw)
     if scratch_pieces is not None:
         extra["scratch"] = env.turn_value_rollout_scratch(scratch_pieces)
     got = launch(env, plies, table, i32(white), i32(black), **extra)
-    counts = check_against_two_net(rules, B, plies, nets, white, black, got, env, max_steps, state, what, **kw)
+    counts = check_against_two_net(rules, B, plies, nets, white, black, got, env, max_steps, state, what, env_seed, **kw)
     return env, got, counts
 
 
@@ -203,6 +207,34 @@ def test_per_env_equality_full4(nets):
     assert_same_env(small, whole)
     small.close()
     whole.close()
+
+
+def test_full4_a_level_past_the_chip_tier_walks_in_the_slab(nets):
+    """big_state() (2,065 rows under 1-1: a level past the 256-node tier, so
+    the walk runs again in the wave's slab piece) on exactly the envs of a
+    B = 64 batch whose first roll is 1-1 (BIG_SEED: SEED's first rolls have no
+    1-1 among 64 envs); white, big_state()'s mover, has a net in every pair; 3
+    pieces of scratch, so an overflowing env shares its wave's piece with the
+    envs before and behind it."""
+    B, plies = 64, 2
+    pairs = [(0, 1), (1, -1), (2, 3), (3, 0)]
+    probe = make_env(B, rules="full4", seed=BIG_SEED)
+    first = np_(probe.dice())
+    base = {k: np_(v) for k, v in probe.get_state().items()}
+    ones = np.flatnonzero((first == 1).all(1))
+    assert len(ones) >= 1, "no env of the batch rolls 1-1 first: choose another seed"
+    big = big_state()
+    assert big["player"] == 1
+    board, off, ft, player = (base[k].copy() for k in ("board", "off", "first_turn", "player"))
+    board[ones], off[ones], ft[ones], player[ones] = big["board"], big["off"], big["ft"], big["player"]
+    probe.set_state(*(torch.as_tensor(a).to(probe.device) for a in (board, off, ft, player)))
+    rows = np.diff(np_(probe.turn_afterstates(feat=False).offsets))
+    assert (rows[ones] == BIG_ROWS).all() and rows.max() == BIG_ROWS
+    probe.close()
+    env, _, counts = run_case("full4", B, plies, nets, pairs=pairs, state=(board, off, ft, player), scratch_pieces=3,
+                              what="full4 big_state on the 1-1 envs", env_seed=BIG_SEED)
+    assert len(counts) == 4
+    env.close()
 
 
 @pytest.mark.parametrize("rules", RULES)
