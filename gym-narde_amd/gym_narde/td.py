@@ -51,9 +51,14 @@ from .value_net import HIDDEN_ACTS, OUT_ACTS
 from .value_play import ValuePlayer
 
 
-def _check_learner(name, env, net, lam):
+def _need_mlp(name, net):
+    """net quacks like a value_net.ValueMLP, or `name`'s TypeError."""
     if not (hasattr(net, "struct") and hasattr(net, "pack")):
         raise TypeError(f"{name} needs a gym_narde.value_net.ValueMLP")
+
+
+def _check_learner(name, env, net, lam):
+    _need_mlp(name, net)
     if not env.autoreset:
         raise ValueError(f"{name} needs an env with autoreset=True")
     if net.l1.weight.device != env.device:
@@ -108,8 +113,7 @@ class _ValueOptimizer:
     def __init__(self, net, max_grad_norm):
         import torch as t
 
-        if not (hasattr(net, "struct") and hasattr(net, "pack")):
-            raise TypeError(f"{type(self).__name__} needs a gym_narde.value_net.ValueMLP")
+        _need_mlp(type(self).__name__, net)
         if not net.l1.weight.is_cuda:
             raise ValueError(f"{type(self).__name__} needs a net on a GPU device: the steps are device kernels")
         if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
@@ -233,7 +237,41 @@ class ValueAdam(_ValueOptimizer):
         return 8 * self.rows + 24 + (0 if self.norm is None else 8)
 
 
-class WindowTDLambdaLearner:
+class _SelfPlayWindow:
+    """What the three windowed learners share: a window of `plies` plies of
+    self-play in one launch, the net on both sides, into buffers with records
+    (bufs); the FULL4 launch's scratch (_roll_scratch); the explore pair on
+    the device (_eps, _tag: None for greedy play); the count of windows
+    played."""
+
+    def _make_window(self, env, net, plies, epsilon, seed):
+        t, z = env.torch, dict(device=env.device)
+        self.env, self.net, self.plies, self.seed = env, net, int(plies), int(seed)
+        self.windows = 0
+        self.bufs = env._twin("value_rollout_buffers")(self.plies, records=True)
+        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
+        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
+        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
+
+    def play(self):
+        """The window's plies in one launch, the net on both sides; the
+        explore tag advances by them.  Returns the launch's buffers."""
+        kw = {} if self._roll_scratch is None else dict(scratch=self._roll_scratch)
+        self.env._twin("value_rollout")(self.plies, self.net, epsilon=self._eps, tag=self._tag, seed=self.seed,
+                                        bufs=self.bufs, **kw)
+        if self._tag is not None:
+            self._tag += self.plies
+        self.windows += 1
+        return self.bufs
+
+    def _window_bytes(self):
+        own = [x for x in self.bufs.values() if x is not None]
+        if self._roll_scratch is not None:
+            own.append(self._roll_scratch)
+        return sum(x.numel() * x.element_size() for x in own)
+
+
+class WindowTDLambdaLearner(_SelfPlayWindow):
     """env: a VecNardeEnv (either rule set) with autoreset; net: a ValueMLP on
     its device.  alpha: step size; lam: the return's decay; plies: the
     window K; gamma: the discount; epsilon: the explore probability of the
@@ -248,31 +286,14 @@ class WindowTDLambdaLearner:
         _check_optimizer("WindowTDLambdaLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1:
             raise ValueError("plies must be >= 1")
-        self.env, self.net, self.plies = env, net, int(plies)
+        self._make_window(env, net, plies, epsilon, seed)
         self.alpha = None if alpha is None else float(alpha)
-        self.lam, self.gamma, self.seed = float(lam), float(gamma), int(seed)
+        self.lam, self.gamma = float(lam), float(gamma)
         self.optimizer, self.grad_hook, self.grad = optimizer, grad_hook, None
         z = dict(device=env.device)
-        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
-        self.bufs = make(self.plies, records=True)
         self.delta = t.zeros((self.plies, env.num_envs), dtype=t.float32, **z)
         self.scratch = t.empty(_lib.td_window_scratch_floats(env.num_envs, self.plies, net.hidden), dtype=t.float32, **z)
-        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
-        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
-        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
         self._mlp = _train_struct(env, net)
-
-    def play(self):
-        """The window's K plies in one launch, the net on both sides; the
-        explore tag advances by K.  Returns the launch's buffers."""
-        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
-        if env.full:
-            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
-        else:
-            env.value_rollout(self.plies, self.net, **kw)
-        if self._tag is not None:
-            self._tag += self.plies
-        return self.bufs
 
     def update(self):
         """One weight update from the window play() recorded."""
@@ -319,12 +340,8 @@ class WindowTDLambdaLearner:
 
     def memory_bytes(self):
         """Device memory the learner owns."""
-        own = [x for x in self.bufs.values() if x is not None] + [self.delta, self.scratch]
-        if self._roll_scratch is not None:
-            own.append(self._roll_scratch)
-        if self.grad is not None:
-            own.append(self.grad)
-        return sum(x.numel() * x.element_size() for x in own)
+        own = [self.delta, self.scratch] + ([] if self.grad is None else [self.grad])
+        return self._window_bytes() + sum(x.numel() * x.element_size() for x in own)
 
 
 class ValueFitter:
@@ -339,8 +356,7 @@ class ValueFitter:
 
     def __init__(self, env, net, n, optimizer=None, grad_hook=None):
         t = env.torch
-        if not (hasattr(net, "struct") and hasattr(net, "pack")):
-            raise TypeError("ValueFitter needs a gym_narde.value_net.ValueMLP")
+        _need_mlp("ValueFitter", net)
         if net.l1.weight.device != env.device:
             raise ValueError(f"the net is on {net.l1.weight.device}, the env on {env.device}")
         if int(n) < 1:
@@ -428,7 +444,7 @@ class ValueFitter:
         return sum(x.numel() * x.element_size() for x in own)
 
 
-class PlayoutTargetLearner:
+class PlayoutTargetLearner(_SelfPlayWindow):
     """Self-play, playouts of its positions, a fit onto their means (DESIGN.md
     section 24).  env: a VecNardeEnv (either rule set) with autoreset; net: a
     ValueMLP on its device.  Every step: play() -- `plies` plies of
@@ -454,38 +470,19 @@ class PlayoutTargetLearner:
         _check_optimizer("PlayoutTargetLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1 or int(trials) < 1 or int(every) < 1 or int(max_plies) < 1:
             raise ValueError("plies, trials, every and max_plies must be >= 1")
-        self.env, self.net, self.plies, self.trials = env, net, int(plies), int(trials)
-        self.every, self.max_plies, self.leaf = int(every), int(max_plies), bool(leaf)
+        self._make_window(env, net, plies, epsilon, seed)
+        self.trials, self.every, self.max_plies, self.leaf = int(trials), int(every), int(max_plies), bool(leaf)
         self.playout_net = net if playout_net is None else playout_net
         self.alpha = None if alpha is None else float(alpha)
-        self.seed, self.common_dice = int(seed), bool(common_dice)
-        self.windows = 0
+        self.common_dice = bool(common_dice)
         z = dict(device=env.device)
         B, M = env.num_envs, -(-self.plies // self.every)
         N = M * B
-        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
-        self.bufs = make(self.plies, records=True)
         self.roots = t.zeros((N, 8), dtype=t.int32, **z)
         self.result = None  # the playouts' PlayoutResult, made by the first targets()
         self.target = t.zeros(N, dtype=t.float32, **z)
         self.weight = t.zeros(N, dtype=t.float32, **z)
         self.fitter = ValueFitter(env, net, N, optimizer=optimizer, grad_hook=grad_hook)
-        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
-        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
-        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
-
-    def play(self):
-        """The window's plies in one launch, the net on both sides; the
-        explore tag advances by them.  Returns the launch's buffers."""
-        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
-        if env.full:
-            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
-        else:
-            env.value_rollout(self.plies, self.net, **kw)
-        if self._tag is not None:
-            self._tag += self.plies
-        self.windows += 1
-        return self.bufs
 
     def targets(self):
         """Playouts of the window's positions and their targets.  Returns
@@ -515,16 +512,14 @@ class PlayoutTargetLearner:
 
     def memory_bytes(self):
         """Device memory the learner owns."""
-        own = [x for x in self.bufs.values() if x is not None] + [self.roots, self.target, self.weight]
+        own = [self.roots, self.target, self.weight]
         if self.result is not None:
             own += [x for x in (self.result.sums, self.result.outcome, self.result.length, self.result.leaf)
                     if x is not None]
-        if self._roll_scratch is not None:
-            own.append(self._roll_scratch)
-        return sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
+        return self._window_bytes() + sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
 
 
-class LookaheadTargetLearner:
+class LookaheadTargetLearner(_SelfPlayWindow):
     """Self-play and a fit onto the two-ply values of its positions (DESIGN.md
     section 25): PlayoutTargetLearner with VecNardeEnv.lookahead_records() in
     place of the playouts.  env: a VecNardeEnv (either rule set) with
@@ -546,34 +541,15 @@ class LookaheadTargetLearner:
         _check_optimizer("LookaheadTargetLearner", env, net, alpha, optimizer, grad_hook)
         if int(plies) < 1 or int(every) < 1:
             raise ValueError("plies and every must be >= 1")
-        self.env, self.net, self.plies, self.every = env, net, int(plies), int(every)
-        self.alpha, self.seed = None if alpha is None else float(alpha), int(seed)
-        self.windows = 0
+        self._make_window(env, net, plies, epsilon, seed)
+        self.every, self.alpha = int(every), None if alpha is None else float(alpha)
         z = dict(device=env.device)
         B, M = env.num_envs, -(-self.plies // self.every)
         N = M * B
-        make = env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers
-        self.bufs = make(self.plies, records=True)
         self.roots = t.zeros((N, 8), dtype=t.int32, **z)
         self.target = t.zeros(N, dtype=t.float32, **z)
         self.weight = t.zeros(N, dtype=t.float32, **z)
         self.fitter = ValueFitter(env, net, N, optimizer=optimizer, grad_hook=grad_hook)
-        self._roll_scratch = env.turn_value_rollout_scratch() if env.full else None
-        self._eps = None if epsilon is None else t.tensor(float(epsilon), dtype=t.float32, **z)
-        self._tag = None if epsilon is None else t.zeros((), dtype=t.int64, **z)
-
-    def play(self):
-        """The window's plies in one launch, the net on both sides; the
-        explore tag advances by them.  Returns the launch's buffers."""
-        env, kw = self.env, dict(epsilon=self._eps, tag=self._tag, seed=self.seed, bufs=self.bufs)
-        if env.full:
-            env.turn_value_rollout(self.plies, self.net, scratch=self._roll_scratch, **kw)
-        else:
-            env.value_rollout(self.plies, self.net, **kw)
-        if self._tag is not None:
-            self._tag += self.plies
-        self.windows += 1
-        return self.bufs
 
     def targets(self):
         """The two-ply values of the window's positions.  Returns (target,
@@ -603,10 +579,8 @@ class LookaheadTargetLearner:
     def memory_bytes(self):
         """Device memory the learner owns (the env keeps lookahead_records()'
         scratch of a rules="full4" env)."""
-        own = [x for x in self.bufs.values() if x is not None] + [self.roots, self.target, self.weight]
-        if self._roll_scratch is not None:
-            own.append(self._roll_scratch)
-        return sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
+        own = [self.roots, self.target, self.weight]
+        return self._window_bytes() + sum(x.numel() * x.element_size() for x in own) + self.fitter.memory_bytes()
 
 
 class TDLambdaLearner:
@@ -618,8 +592,7 @@ class TDLambdaLearner:
 
     def __init__(self, env, net, alpha, lam, gamma=1.0, epsilon=None, seed=0, cap=None):
         t = env.torch
-        if not (hasattr(net, "struct") and hasattr(net, "pack")):
-            raise TypeError("TDLambdaLearner needs a gym_narde.value_net.ValueMLP")
+        _need_mlp("TDLambdaLearner", net)
         if not env.autoreset:
             raise ValueError("TDLambdaLearner needs an env with autoreset=True")
         if net.l1.weight.device != env.device:
@@ -649,14 +622,7 @@ class TDLambdaLearner:
 
     def struct(self):
         """The ctypes narde_value_mlp_train over the net's live tensors."""
-        net, t = self.net, self.env.torch
-        net.struct()  # packs _w1t on first use, checks the parameters
-        w = net.l1.weight
-        if w.dtype != t.float32 or not w.is_contiguous():
-            raise ValueError("the learner needs a contiguous float32 l1.weight")
-        return _lib.ValueMlpTrain(net._w1t.data_ptr(), net.hidden, net.l1.bias.data_ptr(), net.l2.weight.data_ptr(),
-                                  net.l2.bias.data_ptr(), net.hidden, HIDDEN_ACTS[net.hidden_act],
-                                  OUT_ACTS[net.out_act], w.data_ptr(), w.stride(0))
+        return _train_struct(self.env, self.net)
 
     def trace_pass(self, decay=None):
         """v, black and the traces from the envs' records as they stand."""

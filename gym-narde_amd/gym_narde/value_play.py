@@ -27,6 +27,11 @@ turn_value_rollout_league(): a net per env and colour from a table).
 """
 
 
+def _is_mlp(net):
+    """net quacks like a value_net.ValueMLP (struct() and pack())."""
+    return hasattr(net, "struct") and hasattr(net, "pack")
+
+
 class ValuePlayer:
     """net: a callable (R,198) float32 -> (R,) or (R,1) values (a
     torch.nn.Module on the env's device).  perspective "white": the values
@@ -46,16 +51,15 @@ class ValuePlayer:
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
         self.env, self.net, self.perspective = env, net, perspective
-        self._expand, self._pick = ((env.turn_afterstates, env.pick_turn) if env.full else
-                                    (env.afterstates, env.pick_afterstate))
-        is_mlp = hasattr(net, "struct") and hasattr(net, "pack")
+        self._expand, self._pick = env._twin("afterstates"), env._twin("pick_afterstate")
+        is_mlp = _is_mlp(net)
         if fused and not is_mlp:
             raise TypeError("fused=True needs a gym_narde.value_net.ValueMLP")
         self.fused = is_mlp if fused is None else bool(fused)
         if cap is not None and not self.fused:
             raise ValueError("cap is the fused path's")
         self.cap = None if cap is None else int(cap)
-        self._scored = env.scored_turn_afterstates if env.full else env.scored_afterstates
+        self._scored = env._twin("scored_afterstates")
         if plies not in (1, 2):
             raise ValueError("plies must be 1 or 2")
         if plies == 2:
@@ -68,7 +72,7 @@ class ValuePlayer:
             if env.full:
                 raise ValueError('plies=2 is rules="ref2" only')
         self.plies = plies
-        self._lookahead = env.lookahead_afterstates
+        self._lookahead = env._twin("lookahead_afterstates")
 
     def values(self, aft):
         """net(feat), with the rows that end the game set to their known
@@ -127,18 +131,17 @@ class LookaheadPlayer(ValuePlayer):
     def __init__(self, env, net, cap=None, top=None):
         from . import _lib
 
-        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+        if not _is_mlp(net):
             raise TypeError("LookaheadPlayer needs a gym_narde.value_net.ValueMLP")
         super().__init__(env, net, perspective="white", fused=True, cap=cap, plies=1)
         self.plies = 2
-        self._lookahead = env.lookahead_turn_afterstates if env.full else env.lookahead_afterstates
         if top is not None:
             if isinstance(top, bool) or not isinstance(top, int):
                 raise TypeError("top must be None or an int")
             if not 1 <= top <= _lib.TOPK_MAX:
                 raise ValueError(f"top must be in 1 .. {_lib.TOPK_MAX}")
         self.top = top
-        self._recorded = env.recorded_turn_afterstates if env.full else env.recorded_afterstates
+        self._recorded = env._twin("recorded_afterstates")
 
     def step(self, epsilon=None, tag=None, seed=0):
         if self.top is None:
@@ -178,7 +181,7 @@ class PlayoutPlayer:
 
     def __init__(self, env, net, k=4, trials=64, max_plies=400, playout_net=None, common_dice=True, truncated=False,
                  cap=None, seed=0):
-        if not (hasattr(net, "struct") and hasattr(net, "pack")):
+        if not _is_mlp(net):
             raise TypeError("PlayoutPlayer needs a gym_narde.value_net.ValueMLP")
         self.env, self.net = env, net
         self.playout_net = net if playout_net is None else playout_net
@@ -186,7 +189,7 @@ class PlayoutPlayer:
         self.common_dice, self.truncated = bool(common_dice), bool(truncated)
         self.cap = None if cap is None else int(cap)
         self.seed = int(seed)
-        self._recorded = env.recorded_turn_afterstates if env.full else env.recorded_afterstates
+        self._recorded = env._twin("recorded_afterstates")
         self.sync_ply()
 
     def sync_ply(self):
@@ -227,7 +230,7 @@ def play_match(env, net_a, net_b, plies, epsilon=None, seed=0):
     "points_b"}, "a_black": {...}} from env.stats() after each launch."""
     if env.full:
         raise ValueError('play_match() is rules="ref2" only')
-    return _match(env, env.value_rollout_buffers, "actions", env.value_rollout, net_a, net_b, plies, epsilon, seed)
+    return _match(env, net_a, net_b, plies, epsilon, seed)
 
 
 def play_turn_match(env, net_a, net_b, plies, epsilon=None, seed=0):
@@ -236,17 +239,15 @@ def play_turn_match(env, net_a, net_b, plies, epsilon=None, seed=0):
     (DESIGN.md section 20).  The same arguments and the same dictionary."""
     if not env.full:
         raise ValueError('play_turn_match() is rules="full4" only')
-    return _match(env, env.turn_value_rollout_buffers, "play", env.turn_value_rollout, net_a, net_b, plies, epsilon,
-                  seed)
+    return _match(env, net_a, net_b, plies, epsilon, seed)
 
 
-def _match(env, buffers, column, rollout, net_a, net_b, plies, epsilon, seed):
+def _match(env, net_a, net_b, plies, epsilon, seed):
     if net_a is None:
         raise ValueError("net_a is the net under test; pass None as net_b for the random baseline")
     by = {}
-    none = dict(dice=False, value=False, reward=False, terminated=False, truncated=False)
-    none[column] = False
-    bufs = buffers(plies, **none)
+    bufs = env._twin("value_rollout_buffers")(plies, *[False] * 6)  # every per-ply output off
+    rollout = env._twin("value_rollout")
     tag = None if epsilon is None else 0
     for name, white, black in (("a_white", net_a, net_b), ("a_black", net_b, net_a)):
         env.reset()
@@ -368,10 +369,8 @@ def play_league(env, nets, plies, random=False, self_play=False, epsilon=None, s
     white = np.asarray([p[0] for p in pairs], dtype=np.int32)[idx]
     black = np.asarray([p[1] for p in pairs], dtype=np.int32)[idx]
     table = env.net_table(nets)
-    none = dict(dice=False, value=False, reward=False, terminated=False, truncated=False)
-    none["play" if env.full else "actions"] = False
-    bufs = (env.turn_value_rollout_buffers if env.full else env.value_rollout_buffers)(plies, **none)
-    rollout = env.turn_value_rollout_league if env.full else env.value_rollout_league
+    bufs = env._twin("value_rollout_buffers")(plies, *[False] * 6)  # every per-ply output off
+    rollout = env._twin("value_rollout_league")
     env.reset()
     rollout(plies, table, t.as_tensor(white, device=env.device), t.as_tensor(black, device=env.device),
             epsilon=epsilon, tag=None if epsilon is None else 0, seed=seed, bufs=bufs)

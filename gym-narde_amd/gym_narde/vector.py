@@ -121,14 +121,46 @@ Afterstates = collections.namedtuple("Afterstates", "offsets row_env codes feat 
 # VecNardeEnv.turn_afterstates' result (rules="full4"): the same CSR rows with
 # play (R,4,2) int8 (from, die) in place of the action codes
 TurnAfterstates = collections.namedtuple("TurnAfterstates", "offsets row_env play feat obs reward cap")
-# what differs between the two: the C entry points, the tuple, the action
-# column (field, trailing shape, torch dtype), the pick's fill for no row,
-# the lookahead's scratch size
-_RowKind = collections.namedtuple("_RowKind", "expand pick tuple field shape dtype no_row look_scratch")
-_REF2_ROWS = _RowKind("narde_afterstates", "narde_afterstate_pick", Afterstates, "codes", (2,), "int16", 0,
-                      _lib.lookahead_scratch_bytes)
-_FULL4_ROWS = _RowKind("narde_turn_afterstates", "narde_turn_pick", TurnAfterstates, "play", (4, 2), "int8", -1,
-                       _lib.turn_lookahead_scratch_bytes)
+# a rule set as the Python surface sees it (an env's is self._kind): the result
+# tuple; the action column (field, trailing shape, torch dtype) and the picks'
+# fill for no row; the C entry point of every call that has a REF2 / FULL4 twin
+# (expand + "_scored" / "_lookahead" / "_records" are its other forms); whether
+# the twins of the rollouts, playouts and records lookahead take a scratch (the
+# FULL4 ones do); the lookahead's scratch size;
+# the value rollouts' [plies][B] buffers (name, trailing shape, torch dtype);
+# the public methods that are a REF2 method's twin, by that method's name
+# (VecNardeEnv._twin(), for callers that serve both rule sets)
+_RowKind = collections.namedtuple(
+    "_RowKind", "tuple field shape dtype no_row expand pick playout_pick slot_pick records_lookahead value_rollout "
+                "league playout step selfplay rollout turn_scratch look_scratch bufs twins")
+_TWINS = ("afterstates", "scored_afterstates", "lookahead_afterstates", "recorded_afterstates", "pick_afterstate",
+          "value_rollout", "value_rollout_buffers", "value_rollout_league")
+_RECORDS_BUF = ("records", (8,), "int32")
+
+
+_REF2_ROWS = _RowKind(
+    tuple=Afterstates, field="codes", shape=(2,), dtype="int16", no_row=0,
+    expand="narde_afterstates", pick="narde_afterstate_pick", playout_pick="narde_playout_pick",
+    slot_pick="narde_slot_pick", records_lookahead="narde_records_lookahead",
+    value_rollout="narde_value_rollout_records", league="narde_value_rollout_league", playout="narde_value_playout",
+    step="narde_step", selfplay="narde_selfplay", rollout="narde_rollout",
+    turn_scratch=False, look_scratch=_lib.lookahead_scratch_bytes,
+    bufs=(("dice", (2,), "uint8"), ("actions", (2,), "int16"), ("value", (), "float32"), ("reward", (), "int32"),
+          ("terminated", (), "uint8"), ("truncated", (), "uint8")),
+    twins=dict(zip(_TWINS, _TWINS)))
+_FULL4_ROWS = _RowKind(
+    tuple=TurnAfterstates, field="play", shape=(4, 2), dtype="int8", no_row=-1,
+    expand="narde_turn_afterstates", pick="narde_turn_pick", playout_pick="narde_turn_playout_pick",
+    slot_pick="narde_turn_slot_pick", records_lookahead="narde_turn_records_lookahead",
+    value_rollout="narde_turn_value_rollout_records", league="narde_turn_value_rollout_league",
+    playout="narde_turn_value_playout", step="narde_step_full", selfplay="narde_selfplay_full",
+    rollout="narde_rollout_full",
+    turn_scratch=True, look_scratch=_lib.turn_lookahead_scratch_bytes,
+    bufs=(("dice", (2,), "uint8"), ("play", (4, 2), "int8"), ("value", (), "float32"), ("reward", (), "int32"),
+          ("terminated", (), "uint8"), ("truncated", (), "uint8")),
+    twins=dict(zip(_TWINS, ("turn_afterstates", "scored_turn_afterstates", "lookahead_turn_afterstates",
+                            "recorded_turn_afterstates", "pick_turn", "turn_value_rollout",
+                            "turn_value_rollout_buffers", "turn_value_rollout_league"))))
 
 
 _SAME = object()  # value_rollout(): "net_black is net_white"
@@ -205,15 +237,23 @@ class VecNardeEnv:
         self.actions_used = torch.zeros((B, 2), dtype=torch.int16, **z)
         self.played = torch.zeros(B, dtype=torch.int64, **z)
         self._look_scratch = None  # the lookahead calls' row records, made on the first call
-        # per-call plumbing of step(), resolved once: the bound entry point and
-        # the output buffers' pointers (they never move)
-        lib = self.handle.lib
-        self._step_fn = lib.narde_step_full if self.full else lib.narde_step
-        self._step_out = tuple(_lib.ptr(t) for t in (
-            (self.obs, self.reward, self.terminated, self.truncated, self.legal, self.played) if self.full else
-            (self.obs, self.reward, self.terminated, self.truncated, self.legal, self.actions_used)))
+        self._bind()
 
     # ------------------------------------------------------------ plumbing
+    def _bind(self):
+        """What __init__ resolves once from the rule set, the handle and the
+        step buffers: the rule set's descriptor, and the per-call plumbing of
+        step() -- the bound entry point and the output buffers' pointers (they
+        never move).  (A method of its own so that a host-only test double,
+        which cannot run __init__, resolves them the same way.)"""
+        self._kind = k = _FULL4_ROWS if self.full else _REF2_ROWS
+        # the value rollouts' buffers as the launches check them: (name, torch dtype, shape behind plies, dtype's name)
+        self._buf_specs = tuple((name, getattr(self.torch, dt), (self.num_envs,) + shape, dt)
+                                for name, shape, dt in k.bufs + (_RECORDS_BUF,))
+        self._step_fn = getattr(self.handle.lib, self._kind.step)
+        self._step_out = tuple(_lib.ptr(t) for t in (self.obs, self.reward, self.terminated, self.truncated, self.legal,
+                                                     self.played if self.full else self.actions_used))
+
     def _s(self):
         return ctypes.c_void_p(self.torch.cuda.current_stream(self.device).cuda_stream)
 
@@ -225,6 +265,11 @@ class VecNardeEnv:
         if tuple(t.shape) != tuple(shape):
             raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         return t
+
+    def _twin(self, name):
+        """The env's method for its rule set that is the REF2 method `name`
+        or its FULL4 twin (for td.py and value_play.py, which serve both)."""
+        return getattr(self, self._kind.twins[name])
 
     @property
     def ply(self):
@@ -393,39 +438,163 @@ class VecNardeEnv:
         self._keep = (d,)
         return actions
 
-    def _expand_rows(self, k, dice, cap, feat, obs, out):
-        """afterstates() / turn_afterstates(): the rows of kind k (a _RowKind)."""
+    # ---------------------------------------- the checks the calls below share
+    def _net_struct(self, net, none=""):
+        """The check of a value net: its struct."""
+        if not hasattr(net, "struct"):
+            raise TypeError(f"net must be a gym_narde.value_net.ValueMLP{none}")
+        mlp = net.struct()
+        if net.l1.weight.device != self.device:
+            raise ValueError("the net must live on the env's device")
+        return mlp
+
+    def _explore(self, epsilon, tag):
+        """The explore pair as device scalars, (None, None) for greedy play."""
+        t = self.torch
+        if (epsilon is None) != (tag is None):
+            raise ValueError("epsilon and tag go together")
+        if epsilon is not None:
+            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
+            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+        return epsilon, tag
+
+    def _check_records(self, a, text, least=1, most=None):
+        """a is an (n, 8) int32 contiguous device tensor of records, least <=
+        n (<= most), or a ValueError of the call's own text."""
+        t = self.torch
+        if (not isinstance(a, t.Tensor) or a.dtype != t.int32 or a.device != self.device or not a.is_contiguous()
+                or a.dim() != 2 or a.shape[1] != 8 or a.shape[0] < least or (most is not None and a.shape[0] > most)):
+            raise ValueError(text)
+
+    def _row_values(self, aft, values):
+        v, dim = values, values.dim()
+        if dim == 2 and v.shape[1] == 1:
+            v, dim = v[:, 0], 1
+        n = v.shape[0] if dim == 1 else -1
+        if (dim != 1 or v.dtype != self.torch.float32 or v.device != self.device or n < aft.cap
+                or (n > 1 and v.stride(0) < 1)):
+            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
+        return v
+
+    def _check_sel(self, sel):
+        """sel is top_rows()' (B, k) int32 tensor: k."""
+        t = self.torch
+        if (not isinstance(sel, t.Tensor) or sel.dim() != 2 or sel.shape[0] != self.num_envs or sel.dtype != t.int32
+                or not sel.is_contiguous() or sel.device != self.device):
+            raise ValueError("sel must be top_rows()' (B, k) int32 tensor")
+        return int(sel.shape[1])
+
+    @staticmethod
+    def _playout_sums(result, leaf):
+        """(sums, trials, the leaf values or None) of a PlayoutResult or a
+        (sums, trials[, leaf]) tuple, for a call with or without leaf."""
+        if isinstance(result, PlayoutResult):
+            sums, trials, lf = result.sums, result.trials, result.leaf
+        else:
+            sums, trials = result[0], int(result[1])
+            lf = result[2] if len(result) > 2 else None
+        if leaf and lf is None:
+            raise ValueError("leaf=True needs the playouts' leaf values (playout(leaf=True))")
+        return sums, trials, lf if leaf else None
+
+    def _pick_out(self, k, slots=None):
+        """New (actions, row[, score (B, slots)]) for a pick over rows of kind k."""
+        t, B = self.torch, self.num_envs
+        out = (t.empty((B,) + k.shape, dtype=getattr(t, k.dtype), device=self.device),
+               t.empty(B, dtype=t.int32, device=self.device))
+        return out if slots is None else out + (t.empty((B, slots), dtype=t.float32, device=self.device),)
+
+    @staticmethod
+    def _no_row(k, out):
+        """A pick's outputs when no env has a row (cap == 0: no call, no array to read)."""
+        for a, fill in zip(out, (k.no_row, -1, float("nan"))):
+            a.fill_(fill)
+        return tuple(out)
+
+    def _turn_scratch(self, scratch, trials=None):
+        """The FULL4 launches' scratch: the caller's, checked; or the env's
+        own -- the rollouts', made once at min(B, resident waves) pieces, or
+        with trials (a playout call's N * trials) the playouts'."""
+        t = self.torch
+        if scratch is not None:
+            if (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
+                    or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
+                raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
+                                 f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
+            return scratch
+        if trials is None:
+            if getattr(self, "_turn_rollout_scratch", None) is None:
+                self._turn_rollout_scratch = self.turn_value_rollout_scratch()
+            return self._turn_rollout_scratch
+        # min(N * trials, resident waves) pieces, kept on the env and grown when a call needs more
+        # (the occupancy query is made once: a later call, inside a graph capture too, makes no other
+        # call than the launch)
+        if getattr(self, "_playout_waves", None) is None:
+            self._playout_waves = self.turn_value_rollout_waves()
+        need = _lib.turn_rollout_scratch_bytes(min(trials, self._playout_waves))
+        if getattr(self, "_playout_scratch", None) is None or self._playout_scratch.numel() < need:
+            self._playout_scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        return self._playout_scratch
+
+    # ------------------------------------------------- the expansions' one core
+    def _count_rows(self, k, d, offsets):
+        """The counts alone (no array to write): the sizing call."""
+        self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+
+    def _new_rows(self, cap, shape, dtype):
+        return self.torch.empty((cap,) + shape, dtype=dtype, device=self.device)
+
+    def _row_cols(self, k, aft, offsets_required=False):
+        """_rows()' columns every rows tuple has ahead of the call's own."""
+        t = self.torch
+        return (("offsets", aft.offsets, (self.num_envs + 1,), t.int32, offsets_required),
+                ("row_env", aft.row_env, (), t.int32, False),
+                (k.field, getattr(aft, k.field), k.shape, getattr(t, k.dtype), False))
+
+    def _rows(self, k, dice, cap, aft, cols, text, feat=False, obs=False):
+        """What every expansion of rows of kind k (a _RowKind) starts with:
+        the dice; then either aft, a caller's tuple of preallocated arrays,
+        checked -- cols: (name, tensor, trailing shape, dtype, required) of
+        every array the call takes, offsets' shape whole; text: "out." or
+        "out ", the call's wording --, or the sizing call when cap is None
+        (the one synchronise) and a new tuple of cap rows.  Returns (dice,
+        the tuple, cap)."""
         B, t = self.num_envs, self.torch
         d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
-        if out is not None:
-            offsets = out.offsets
-            cap = out.cap if cap is None else int(cap)
-            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
-                                       (k.field, getattr(out, k.field), k.shape, getattr(t, k.dtype)),
-                                       ("feat", out.feat, (198,), t.float32), ("obs", out.obs, (24,), t.int32),
-                                       ("reward", out.reward, (), t.int8)):
-                if a is None:
+        if aft is not None:
+            cap = aft.cap if cap is None else int(cap)
+            for name, a, shape, dt, required in cols:
+                if a is None and not required:
                     continue
-                ok = a.dtype == dt and a.device == self.device and a.is_contiguous()
+                ok = a is not None and a.dtype == dt and a.device == self.device and a.is_contiguous()
                 ok = ok and (tuple(a.shape) == shape if name == "offsets" else
                              tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
                 if not ok:
-                    raise ValueError(f"out.{name} must be a contiguous {dt} device tensor of at least cap rows")
+                    raise ValueError(f"{text}{name} must be a contiguous {dt} device tensor of at least cap rows")
         else:
             offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
             if cap is None:
-                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
+                self._count_rows(k, d, offsets)
                 cap = int(offsets[B].item())  # the one synchronise
             cap = int(cap)
             if cap < 0:
                 raise ValueError("cap must be >= 0")
-            mk = lambda on, shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device) if on else None  # noqa: E731
-            out = k.tuple(offsets, mk(True, (), t.int32), mk(True, k.shape, getattr(t, k.dtype)),
-                          mk(feat, (198,), t.float32), mk(obs, (24,), t.int32), mk(True, (), t.int8), cap)
+            aft = k.tuple(offsets, self._new_rows(cap, (), t.int32), self._new_rows(cap, k.shape, getattr(t, k.dtype)),
+                          self._new_rows(cap, (198,), t.float32) if feat else None,
+                          self._new_rows(cap, (24,), t.int32) if obs else None, self._new_rows(cap, (), t.int8), cap)
         if cap < 0:
             raise ValueError("cap must be >= 0")
+        return d, aft, cap
+
+    def _expand_rows(self, k, dice, cap, feat, obs, out):
+        """afterstates() / turn_afterstates(): the rows of kind k."""
+        t = self.torch
+        cols = out and self._row_cols(k, out) + (("feat", out.feat, (198,), t.float32, False),
+                                                 ("obs", out.obs, (24,), t.int32, False),
+                                                 ("reward", out.reward, (), t.int8, False))
+        d, out, cap = self._rows(k, dice, cap, out, cols, "out.", feat=feat, obs=obs)
         rows = (out.row_env, getattr(out, k.field), out.feat, out.obs, out.reward)
-        self.handle.call(k.expand, _lib.ptr(d), cap, _lib.ptr(offsets),
+        self.handle.call(k.expand, _lib.ptr(d), cap, _lib.ptr(out.offsets),
                          *(_lib.ptr(a) if a is not None and cap > 0 else None for a in rows), self._s())
         self._keep = (d,)
         return out._replace(cap=cap)
@@ -436,62 +605,32 @@ class VecNardeEnv:
         the two-ply values (lookahead_afterstates() / lookahead_turn_afterstates())."""
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
-        B, t = self.num_envs, self.torch
-        if not hasattr(net, "struct"):
-            raise TypeError("net must be a gym_narde.value_net.ValueMLP")
-        mlp = net.struct()
-        if net.l1.weight.device != self.device:
-            raise ValueError("the net must live on the env's device")
-        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
-        values = None
+        t = self.torch
+        mlp = self._net_struct(net)
+        values = cols = None
         if out is not None:
             if not hasattr(out, "offsets"):
                 out, values = out
-            offsets = out.offsets
-            cap = out.cap if cap is None else int(cap)
-            if values is None:
-                values = t.empty(cap, dtype=t.float32, device=self.device)
-            for name, a, shape, dt in (("offsets", out.offsets, (B + 1,), t.int32), ("row_env", out.row_env, (), t.int32),
-                                       (k.field, getattr(out, k.field), k.shape, getattr(t, k.dtype)),
-                                       ("reward", out.reward, (), t.int8), ("values", values, (), t.float32)):
-                if a is None and name != "values":
-                    continue
-                ok = a is not None and a.dtype == dt and a.device == self.device and a.is_contiguous()
-                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
-                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
-                if not ok:
-                    raise ValueError(f"out {name} must be a contiguous {dt} device tensor of at least cap rows")
-            out = out._replace(feat=None, obs=None)
+            cols = self._row_cols(k, out) + (("reward", out.reward, (), t.int8, False),
+                                             ("values", values, (), t.float32, False))
+        d, out, cap = self._rows(k, dice, cap, out, cols, "out ")
+        if values is None:
+            values = self._new_rows(cap, (), t.float32)
+        if cap == 0:
+            self._count_rows(k, d, out.offsets)
         else:
-            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
-            if cap is None:
-                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
-                cap = int(offsets[B].item())  # the one synchronise
-            cap = int(cap)
-            if cap < 0:
-                raise ValueError("cap must be >= 0")
-            mk = lambda shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device)  # noqa: E731
-            out = k.tuple(offsets, mk((), t.int32), mk(k.shape, getattr(t, k.dtype)), None, None, mk((), t.int8), cap)
-            values = mk((), t.float32)
-        if cap < 0:
-            raise ValueError("cap must be >= 0")
-        if cap == 0:  # the counts alone (no array to write)
-            self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
-        else:
-            rows = (out.row_env, getattr(out, k.field), out.reward)
+            args = (_lib.ptr(d), cap, _lib.ptr(out.offsets), _lib.ptr(out.row_env), _lib.ptr(getattr(out, k.field)),
+                    _lib.ptr(out.reward), ctypes.byref(mlp), PERSPECTIVES[perspective], _lib.ptr(values))
             if lookahead:
                 need = k.look_scratch(cap)
                 if self._look_scratch is None or self._look_scratch.numel() < need:  # grown only when cap grows
                     self._look_scratch = t.empty(need, dtype=t.uint8, device=self.device)
-                self.handle.call(k.expand + "_lookahead", _lib.ptr(d), cap, _lib.ptr(offsets),
-                                 *(_lib.ptr(a) for a in rows), ctypes.byref(mlp), PERSPECTIVES[perspective],
-                                 _lib.ptr(values), _lib.ptr(self._look_scratch), self._look_scratch.numel(), self._s())
+                self.handle.call(k.expand + "_lookahead", *args, _lib.ptr(self._look_scratch),
+                                 self._look_scratch.numel(), self._s())
             else:
-                self.handle.call(k.expand + "_scored", _lib.ptr(d), cap, _lib.ptr(offsets),
-                                 *(_lib.ptr(a) for a in rows), ctypes.byref(mlp), PERSPECTIVES[perspective],
-                                 _lib.ptr(values), self._s())
+                self.handle.call(k.expand + "_scored", *args, self._s())
         self._keep = (d, net)
-        return out._replace(cap=cap), values[:cap]
+        return out._replace(feat=None, obs=None, cap=cap), values[:cap]
 
     def scored_afterstates(self, net, dice=None, cap=None, perspective="white", out=None):
         """afterstates() with the rows scored on the way (narde_afterstates_scored;
@@ -557,53 +696,30 @@ class VecNardeEnv:
     def _recorded_rows(self, k, net, dice, cap, out):
         """recorded_afterstates() / recorded_turn_afterstates(): the rows of
         kind k with their records, and their values when net is given."""
-        B, t = self.num_envs, self.torch
-        mlp = None
-        if net is not None:
-            if not hasattr(net, "struct"):
-                raise TypeError("net must be a gym_narde.value_net.ValueMLP or None")
-            mlp = net.struct()
-            if net.l1.weight.device != self.device:
-                raise ValueError("the net must live on the env's device")
-        d = None if dice is None else self._dev(dice, t.uint8, (B, 2))
+        t = self.torch
+        mlp = None if net is None else self._net_struct(net, none=" or None")
+        aft = values = records = cols = None
         if out is not None:
             aft, values, records = out
-            cap = aft.cap if cap is None else int(cap)
-            if cap < 0:
+            if (aft.cap if cap is None else int(cap)) < 0:  # (this call looks at cap before its arrays)
                 raise ValueError("cap must be >= 0")
-            for name, a, shape, dt in (("offsets", aft.offsets, (B + 1,), t.int32), ("row_env", aft.row_env, (), t.int32),
-                                       (k.field, getattr(aft, k.field), k.shape, getattr(t, k.dtype)),
-                                       ("reward", aft.reward, (), t.int8), ("values", values, (), t.float32),
-                                       ("records", records, (8,), t.int32)):
-                if a is None and (name in ("row_env", k.field, "reward") or (name == "values" and net is None)):
-                    continue
-                ok = a is not None and a.dtype == dt and a.device == self.device and a.is_contiguous()
-                ok = ok and (tuple(a.shape) == shape if name == "offsets" else
-                             tuple(a.shape[1:]) == shape and a.shape[0] >= cap)
-                if not ok:
-                    raise ValueError(f"out {name} must be a contiguous {dt} device tensor of at least cap rows")
-            aft = aft._replace(feat=None, obs=None)
-        else:
-            offsets = t.empty(B + 1, dtype=t.int32, device=self.device)
-            if cap is None:
-                self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(offsets), None, None, None, None, None, self._s())
-                cap = int(offsets[B].item())  # the one synchronise
-            cap = int(cap)
-            if cap < 0:
-                raise ValueError("cap must be >= 0")
-            mk = lambda shape, dt: t.empty((cap,) + shape, dtype=dt, device=self.device)  # noqa: E731
-            aft = k.tuple(offsets, mk((), t.int32), mk(k.shape, getattr(t, k.dtype)), None, None, mk((), t.int8), cap)
-            values = mk((), t.float32) if net is not None else None
-            records = mk((8,), t.int32)
-        if cap == 0:  # the counts alone (no array to write)
-            self.handle.call(k.expand, _lib.ptr(d), 0, _lib.ptr(aft.offsets), None, None, None, None, None, self._s())
+            cols = self._row_cols(k, aft, True) + (("reward", aft.reward, (), t.int8, False),
+                                                   ("values", values, (), t.float32, net is not None),
+                                                   ("records", records, (8,), t.int32, True))
+        d, aft, cap = self._rows(k, dice, cap, aft, cols, "out ")
+        if out is None:
+            values = self._new_rows(cap, (), t.float32) if net is not None else None
+            records = self._new_rows(cap, (8,), t.int32)
+        if cap == 0:
+            self._count_rows(k, d, aft.offsets)
         else:
             self.handle.call(k.expand + "_records", _lib.ptr(d), cap, _lib.ptr(aft.offsets), _lib.ptr(aft.row_env),
                              _lib.ptr(getattr(aft, k.field)), _lib.ptr(aft.reward),
                              ctypes.byref(mlp) if mlp is not None else None, PERSPECTIVES["white"],
                              _lib.ptr(values) if net is not None else None, _lib.ptr(records), self._s())
         self._keep = (d, net, mlp)
-        return aft._replace(cap=cap), (values[:cap] if net is not None else None), records[:cap]
+        return (aft._replace(feat=None, obs=None, cap=cap), (values[:cap] if net is not None else None),
+                records[:cap])
 
     def recorded_afterstates(self, net, dice=None, cap=None, out=None):
         """scored_afterstates() (perspective "white") with each row's record
@@ -626,16 +742,6 @@ class VecNardeEnv:
             raise ValueError('recorded_turn_afterstates() is rules="full4" only')
         return self._recorded_rows(_FULL4_ROWS, net, dice, cap, out)
 
-    def _row_values(self, aft, values):
-        t = self.torch
-        v = values
-        if v.dim() == 2 and v.shape[1] == 1:
-            v = v[:, 0]
-        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
-                or (v.shape[0] > 1 and v.stride(0) < 1)):
-            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
-        return v
-
     def top_rows(self, aft, values, k, records=None, perspective="white", out=None):
         """Each env's k best rows of `aft` by `values`, best first
         (narde_rows_topk), under exactly
@@ -652,10 +758,8 @@ class VecNardeEnv:
         if not 1 <= k <= _lib.TOPK_MAX:
             raise ValueError(f"k must be in 1 .. {_lib.TOPK_MAX}")
         v = self._row_values(aft, values)
-        if records is not None and (records.dtype != t.int32 or records.device != self.device
-                                    or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8
-                                    or records.shape[0] < aft.cap):
-            raise ValueError("records must be a contiguous (>= cap, 8) int32 device tensor")
+        if records is not None:
+            self._check_records(records, "records must be a contiguous (>= cap, 8) int32 device tensor", aft.cap)
         if out is not None:
             sel, roots = out
         else:
@@ -687,40 +791,23 @@ class VecNardeEnv:
         score (B, k) float32 -- NaN where a slot is empty); -1 and (0, 0) / an
         all -1 play for an env with no candidate.  out: an earlier call's
         triple to write into.  Call it before the step.  No synchronise."""
-        t, B = self.torch, self.num_envs
-        kind = _FULL4_ROWS if self.full else _REF2_ROWS
-        if isinstance(result, PlayoutResult):
-            sums, trials, lf = result.sums, result.trials, result.leaf
-        else:
-            sums, trials = result[0], int(result[1])
-            lf = result[2] if len(result) > 2 else None
-        if leaf and lf is None:
-            raise ValueError("leaf=True needs the playouts' leaf values (playout(leaf=True))")
-        lf = lf if leaf else None
-        if sel.dim() != 2 or sel.shape[0] != B or sel.dtype != t.int32 or not sel.is_contiguous():
-            raise ValueError("sel must be top_rows()' (B, k) int32 tensor")
-        k = int(sel.shape[1])
+        t, B, kind = self.torch, self.num_envs, self._kind
+        sums, trials, lf = self._playout_sums(result, leaf)
+        k = self._check_sel(sel)
         if (tuple(sums.shape) != (B * k, 4) or sums.dtype != t.int32 or not sums.is_contiguous()
                 or sums.device != self.device):
             raise ValueError("result must hold the sums of B * k roots")
         if lf is not None and (tuple(lf.shape) != (B * k, trials) or lf.dtype != t.float32 or not lf.is_contiguous()):
             raise ValueError("leaf must be (B * k, trials) float32")
         v = self._row_values(aft, values)
-        if out is not None:
-            actions, row, score = out
-        else:
-            actions = t.empty((B,) + kind.shape, dtype=getattr(t, kind.dtype), device=self.device)
-            row = t.empty(B, dtype=t.int32, device=self.device)
-            score = t.empty((B, k), dtype=t.float32, device=self.device)
-        if aft.cap == 0:  # no row anywhere (and no array to read)
-            actions.fill_(kind.no_row)
-            row.fill_(-1)
-            score.fill_(float("nan"))
-            return actions, row, score
-        self.handle.call("narde_turn_playout_pick" if self.full else "narde_playout_pick", k, _lib.ptr(sel), aft.cap,
-                         _lib.ptr(v), max(1, v.stride(0)), _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)),
-                         trials, _lib.ptr(sums), _lib.ptr(lf), _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score),
-                         self._s())
+        if out is None:
+            out = self._pick_out(kind, k)
+        if aft.cap == 0:
+            return self._no_row(kind, out)
+        actions, row, score = out
+        self.handle.call(kind.playout_pick, k, _lib.ptr(sel), aft.cap, _lib.ptr(v), max(1, v.stride(0)),
+                         _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)), trials, _lib.ptr(sums), _lib.ptr(lf),
+                         _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score), self._s())
         self._keep = (v, sel, sums, lf)
         return actions, row, score
 
@@ -743,32 +830,24 @@ class VecNardeEnv:
         kept on the env and grown when a later call has more records -- a
         caller capturing a graph makes its first call outside capture, with its
         largest n.  No synchronise."""
-        t = self.torch
-        if (not isinstance(records, t.Tensor) or records.dtype != t.int32 or records.device != self.device
-                or not records.is_contiguous() or records.dim() != 2 or records.shape[1] != 8 or records.shape[0] < 1):
-            raise ValueError("records must be a contiguous (n, 8) int32 device tensor of records, n >= 1")
-        if not hasattr(net, "struct"):
-            raise TypeError("net must be a gym_narde.value_net.ValueMLP")
-        mlp = net.struct()
-        if net.l1.weight.device != self.device:
-            raise ValueError("the net must live on the env's device")
+        t, kind = self.torch, self._kind
+        self._check_records(records, "records must be a contiguous (n, 8) int32 device tensor of records, n >= 1")
+        mlp = self._net_struct(net)
         n = int(records.shape[0])
         if out is None:
             out = t.empty(n, dtype=t.float32, device=self.device)
         elif (tuple(out.shape) != (n,) or out.dtype != t.float32 or out.device != self.device
               or not out.is_contiguous()):
             raise ValueError("out must be a contiguous (n,) float32 device tensor")
-        scratch = None
-        if self.full:
-            need = _lib.turn_lookahead_scratch_bytes(n)
+        scratch, tail = None, ()
+        if kind.turn_scratch:
+            need = kind.look_scratch(n)
             if getattr(self, "_records_look_scratch", None) is None or self._records_look_scratch.numel() < need:
                 self._records_look_scratch = t.empty(need, dtype=t.uint8, device=self.device)
             scratch = self._records_look_scratch
-            self.handle.call("narde_turn_records_lookahead", n, _lib.ptr(records), ctypes.byref(mlp), _lib.ptr(out),
-                             _lib.ptr(scratch), int(scratch.numel()), self._s())
-        else:
-            self.handle.call("narde_records_lookahead", n, _lib.ptr(records), ctypes.byref(mlp), _lib.ptr(out),
-                             self._s())
+            tail = (_lib.ptr(scratch), int(scratch.numel()))
+        self.handle.call(kind.records_lookahead, n, _lib.ptr(records), ctypes.byref(mlp), _lib.ptr(out), *tail,
+                         self._s())
         self._keep = (records, net, mlp, out, scratch)
         return out
 
@@ -785,12 +864,8 @@ class VecNardeEnv:
         (B, k) float32); -1 and (0, 0) / an all -1 play for an env with no
         candidate.  out: an earlier call's triple to write into.  Call it
         before the step.  No synchronise."""
-        t, B = self.torch, self.num_envs
-        kind = _FULL4_ROWS if self.full else _REF2_ROWS
-        if (not isinstance(sel, t.Tensor) or sel.dim() != 2 or sel.shape[0] != B or sel.dtype != t.int32
-                or not sel.is_contiguous() or sel.device != self.device):
-            raise ValueError("sel must be top_rows()' (B, k) int32 tensor")
-        k = int(sel.shape[1])
+        t, B, kind = self.torch, self.num_envs, self._kind
+        k = self._check_sel(sel)
         if not 1 <= k <= _lib.TOPK_MAX:
             raise ValueError(f"k must be in 1 .. {_lib.TOPK_MAX}")
         if (not isinstance(slot_score, t.Tensor) or slot_score.dtype != t.float32 or slot_score.device != self.device
@@ -798,20 +873,14 @@ class VecNardeEnv:
                 or tuple(slot_score.shape) not in ((B, k), (B * k,))):
             raise ValueError("slot_score must be a contiguous (B, k) or (B * k,) float32 device tensor")
         v = self._row_values(aft, values)
-        if out is not None:
-            actions, row, score = out
-        else:
-            actions = t.empty((B,) + kind.shape, dtype=getattr(t, kind.dtype), device=self.device)
-            row = t.empty(B, dtype=t.int32, device=self.device)
-            score = t.empty((B, k), dtype=t.float32, device=self.device)
-        if aft.cap == 0:  # no row anywhere (and no array to read)
-            actions.fill_(kind.no_row)
-            row.fill_(-1)
-            score.fill_(float("nan"))
-            return actions, row, score
-        self.handle.call("narde_turn_slot_pick" if self.full else "narde_slot_pick", k, _lib.ptr(sel), aft.cap,
-                         _lib.ptr(v), max(1, v.stride(0)), _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)),
-                         _lib.ptr(slot_score), _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score), self._s())
+        if out is None:
+            out = self._pick_out(kind, k)
+        if aft.cap == 0:
+            return self._no_row(kind, out)
+        actions, row, score = out
+        self.handle.call(kind.slot_pick, k, _lib.ptr(sel), aft.cap, _lib.ptr(v), max(1, v.stride(0)),
+                         _lib.ptr(aft.reward), _lib.ptr(getattr(aft, kind.field)), _lib.ptr(slot_score),
+                         _lib.ptr(actions), _lib.ptr(row), _lib.ptr(score), self._s())
         self._keep = (v, sel, slot_score)
         return actions, row, score
 
@@ -819,29 +888,17 @@ class VecNardeEnv:
         """pick_afterstate() / pick_turn(): the row's action, k.no_row for none."""
         if perspective not in PERSPECTIVES:
             raise ValueError(f"perspective must be one of {tuple(PERSPECTIVES)}")
-        B, t = self.num_envs, self.torch
-        v = values
-        if v.dim() == 2 and v.shape[1] == 1:
-            v = v[:, 0]
-        if (v.dim() != 1 or v.dtype != t.float32 or v.device != self.device or v.shape[0] < aft.cap
-                or (v.shape[0] > 1 and v.stride(0) < 1)):
-            raise ValueError(f"values must be float32, one per afterstate row (at least {aft.cap}), on the env's device")
-        if (epsilon is None) != (tag is None):
-            raise ValueError("epsilon and tag go together")
-        if epsilon is not None:
-            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
-            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
-        actions = t.empty((B,) + k.shape, dtype=getattr(t, k.dtype), device=self.device)
-        row = t.empty(B, dtype=t.int32, device=self.device)
-        if aft.cap == 0:  # no row anywhere (and no array to read)
-            actions.fill_(k.no_row)
-            row.fill_(-1)
-            return actions, row
+        v = self._row_values(aft, values)
+        if epsilon is not None or tag is not None:
+            epsilon, tag = self._explore(epsilon, tag)
+        out = actions, row = self._pick_out(k)
+        if aft.cap == 0:
+            return self._no_row(k, out)
         self.handle.call(k.pick, _lib.ptr(aft.offsets), _lib.ptr(getattr(aft, k.field)), aft.cap, _lib.ptr(v),
                          max(1, v.stride(0)), PERSPECTIVES[perspective], _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1),
                          _lib.ptr(tag), _lib.ptr(actions), _lib.ptr(row), self._s())
         self._keep = (v, epsilon, tag)
-        return actions, row
+        return out
 
     def afterstates(self, dice=None, cap=None, feat=True, obs=False, out=None):
         """The successor positions of each env's roll (narde_afterstates; what
@@ -931,7 +988,7 @@ class VecNardeEnv:
         rc = self._step_fn(self.handle.h, None if a is None else _lib.ptr(a), None if d is None else _lib.ptr(d),
                            *self._step_out, int(self.autoreset), self._s())
         if rc:
-            _lib.check(rc, "narde_step_full" if self.full else "narde_step")
+            _lib.check(rc, self._kind.step)
         if self.full:
             self._keep = (a, d)
             return (self.obs, self.reward, self.terminated, self.truncated,
@@ -941,8 +998,7 @@ class VecNardeEnv:
 
     def selfplay(self, plies):
         """plies plies of random-legal self-play in ONE launch (statistics only)."""
-        self.handle.call("narde_selfplay_full" if self.full else "narde_selfplay", int(plies),
-                         self._s())
+        self.handle.call(self._kind.selfplay, int(plies), self._s())
 
     def rollout_buffers(self, plies, obs=True, reward=True, terminated=True, truncated=True,
                         legal=True, actions=True):
@@ -965,7 +1021,7 @@ class VecNardeEnv:
         for v in bufs.values():
             if v is not None and v.shape[0] < plies:
                 raise ValueError("rollout buffer shorter than plies")
-        self.handle.call("narde_rollout_full" if self.full else "narde_rollout", int(plies),
+        self.handle.call(self._kind.rollout, int(plies),
                          _lib.ptr(bufs["obs"]), _lib.ptr(bufs["reward"]),
                          _lib.ptr(bufs["terminated"]), _lib.ptr(bufs["truncated"]),
                          _lib.ptr(bufs["legal"]), _lib.ptr(bufs["actions"]), self._s())
@@ -979,64 +1035,62 @@ class VecNardeEnv:
         one switched off.  records (off by default): (plies,B,8) int32, each
         env's 32-byte record as the ply found it (what
         td.WindowTDLambdaLearner trains on)."""
-        t, B, dev = self.torch, self.num_envs, self.device
-        plies = int(plies)
-        mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
-        bufs = dict(dice=mk(dice, (plies, B, 2), t.uint8), actions=mk(actions, (plies, B, 2), t.int16),
-                    value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
-                    terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
+        return self._rollout_buffers(_REF2_ROWS, plies, (dice, actions, value, reward, terminated, truncated), records)
+
+    def _rollout_buffers(self, k, plies, on, records=False):
+        """k.bufs as [plies][B] tensors, None where `on` switches one off."""
+        t, B, plies = self.torch, self.num_envs, int(plies)
+        bufs = {name: t.empty((plies, B) + shape, dtype=getattr(t, dt), device=self.device) if flag else None
+                for (name, shape, dt), flag in zip(k.bufs, on)}
         if records:  # (the key exists only then: callers walk the dict)
-            bufs["records"] = t.empty((plies, B, 8), dtype=t.int32, device=dev)
+            bufs["records"] = t.empty((plies, B, 8), dtype=t.int32, device=self.device)
         return bufs
 
-    _VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("actions", (2,), "int16"), ("value", (), "float32"),
-                           ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
-    _RECORDS_BUF = ("records", (8,), "int32")
-
-    def _value_rollout_args(self, plies, net_white, net_black, epsilon, tag, bufs, make_bufs, layout):
-        """value_rollout()'s and turn_value_rollout()'s argument checks: (plies,
-        net_white, net_black, the nets' structs, epsilon, tag, bufs)."""
-        plies = int(plies)
-        if plies < 1:
-            raise ValueError("plies must be >= 1")
+    def _net_pair(self, net_white, net_black):
+        """A launch's net per colour, checked: (net_white, net_black, their
+        structs -- None for a colour that plays the random-legal policy)."""
         if net_black is _SAME:
             net_black = net_white
         if net_white is None and net_black is None:
             raise ValueError("a net for at least one colour (random play on both sides is selfplay())")
-        structs = []
-        for net in (net_white, net_black):
-            if net is None:
-                structs.append(None)
-                continue
-            if not hasattr(net, "struct"):
-                raise TypeError("net must be a gym_narde.value_net.ValueMLP")
-            mlp = net.struct()
-            if net.l1.weight.device != self.device:
-                raise ValueError("the net must live on the env's device")
-            structs.append(mlp)
-        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, make_bufs, layout)
-        return plies, net_white, net_black, structs, epsilon, tag, bufs
+        white = None if net_white is None else self._net_struct(net_white)
+        black = white if net_black is net_white else None if net_black is None else self._net_struct(net_black)
+        return net_white, net_black, [white, black]  # (one struct serves both colours of one net)
 
-    def _value_rollout_bufs(self, plies, epsilon, tag, bufs, make_bufs, layout):
-        """The value rollouts' checks of the explore pair and the buffers (the
-        league launches' too): (epsilon, tag, bufs)."""
-        t, B = self.torch, self.num_envs
-        if (epsilon is None) != (tag is None):
-            raise ValueError("epsilon and tag go together")
-        if epsilon is not None:
-            epsilon = t.as_tensor(epsilon, dtype=t.float32, device=self.device).reshape(())
-            tag = t.as_tensor(tag, dtype=t.int64, device=self.device).reshape(())
+    def _value_rollout(self, entry, plies, who, epsilon, tag, seed, bufs, scratch, league=False):
+        """The one launch body of value_rollout(), turn_value_rollout() and
+        their league twins, by the env's rule set: the checks in their order
+        -- plies, who plays (net_white, net_black; a league's table, white,
+        black), the explore pair, the buffers, the scratch -- and the call."""
+        k, plies = self._kind, int(plies)
+        if plies < 1:
+            raise ValueError("plies must be >= 1")
+        if league:
+            table, white, black = who
+            head = (_lib.ptr(table), self._league_args(table, white, black), _lib.ptr(white), _lib.ptr(black))
+        else:
+            who = _, _, (mw, mb) = self._net_pair(*who)
+            head = (None if mw is None else ctypes.byref(mw), None if mb is None else ctypes.byref(mb))
+        if epsilon is not None or tag is not None:
+            epsilon, tag = self._explore(epsilon, tag)
         if bufs is None:
-            bufs = make_bufs(plies)
-        for name, shape, dt in layout + (self._RECORDS_BUF,):
+            bufs = self._rollout_buffers(k, plies, (True,) * len(k.bufs))
+        ptrs = []  # the buffers' pointers in the launch's order, the records' last
+        for name, dtype, shape, dt in self._buf_specs:
             a = bufs.get(name)
-            if a is None:
-                continue
-            if (a.dtype != getattr(t, dt) or a.device != self.device or not a.is_contiguous()
-                    or a.dim() != 2 + len(shape) or a.shape[0] < plies or tuple(a.shape[1:]) != (B,) + shape):
+            if a is not None and (a.dtype != dtype or a.device != self.device or not a.is_contiguous() or a.dim() < 2
+                                  or a.shape[0] < plies or tuple(a.shape[1:]) != shape):
                 raise ValueError(f"bufs[{name!r}] must be a contiguous {dt} device tensor of shape "
-                                 f"(>= {plies}, {B}{''.join(f', {k}' for k in shape)})")
-        return epsilon, tag, bufs
+                                 f"(>= {plies}{''.join(f', {n}' for n in shape)})")
+            ptrs.append(_lib.ptr(a))
+        tail = keep = ()
+        if k.turn_scratch:
+            scratch = self._turn_scratch(scratch)
+            tail, keep = (_lib.ptr(scratch), int(scratch.numel())), (scratch,)
+        self.handle.call(entry, plies, *head, _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
+                         *ptrs[:-1], *tail, ptrs[-1], self._s())
+        self._keep = who + (epsilon, tag, bufs) + keep
+        return bufs
 
     def value_rollout(self, plies, net_white, net_black=_SAME, epsilon=None, tag=None, seed=0, bufs=None):
         """plies plies of value-greedy play in ONE launch, a net per colour
@@ -1059,33 +1113,15 @@ class VecNardeEnv:
         through pointers: call net.pack() after changing them)."""
         if self.full:
             raise ValueError('value_rollout() is rules="ref2" only')
-        plies, net_white, net_black, structs, epsilon, tag, bufs = self._value_rollout_args(
-            plies, net_white, net_black, epsilon, tag, bufs, self.value_rollout_buffers, self._VALUE_ROLLOUT_BUFS)
-        self.handle.call("narde_value_rollout_records", plies,
-                         *(ctypes.byref(m) if m is not None else None for m in structs),
-                         _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
-                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS),
-                         _lib.ptr(bufs.get("records")), self._s())
-        self._keep = (net_white, net_black, structs, epsilon, tag, bufs)
-        return bufs
+        return self._value_rollout(self._kind.value_rollout, plies, (net_white, net_black), epsilon, tag, seed, bufs,
+                                   None)
 
     def turn_value_rollout_buffers(self, plies, dice=True, play=True, value=True, reward=True, terminated=True,
                                    truncated=True, records=False):
         """Allocate turn_value_rollout()'s [plies][B] buffers:
         value_rollout_buffers() with play (plies,B,4,2) int8 -- the (from,
         die) sub-moves, -1 padded -- in place of actions."""
-        t, B, dev = self.torch, self.num_envs, self.device
-        plies = int(plies)
-        mk = lambda on, shape, dt: t.empty(shape, dtype=dt, device=dev) if on else None  # noqa: E731
-        bufs = dict(dice=mk(dice, (plies, B, 2), t.uint8), play=mk(play, (plies, B, 4, 2), t.int8),
-                    value=mk(value, (plies, B), t.float32), reward=mk(reward, (plies, B), t.int32),
-                    terminated=mk(terminated, (plies, B), t.uint8), truncated=mk(truncated, (plies, B), t.uint8))
-        if records:  # (the key exists only then: callers walk the dict)
-            bufs["records"] = t.empty((plies, B, 8), dtype=t.int32, device=dev)
-        return bufs
-
-    _TURN_VALUE_ROLLOUT_BUFS = (("dice", (2,), "uint8"), ("play", (4, 2), "int8"), ("value", (), "float32"),
-                                ("reward", (), "int32"), ("terminated", (), "uint8"), ("truncated", (), "uint8"))
+        return self._rollout_buffers(_FULL4_ROWS, plies, (dice, play, value, reward, terminated, truncated), records)
 
     def turn_value_rollout_waves(self):
         """The waves the device keeps resident for turn_value_rollout()'s
@@ -1130,25 +1166,8 @@ class VecNardeEnv:
         tensors."""
         if not self.full:
             raise ValueError('turn_value_rollout() is rules="full4" only')
-        t = self.torch
-        plies, net_white, net_black, structs, epsilon, tag, bufs = self._value_rollout_args(
-            plies, net_white, net_black, epsilon, tag, bufs, self.turn_value_rollout_buffers,
-            self._TURN_VALUE_ROLLOUT_BUFS)
-        if scratch is None:
-            if getattr(self, "_turn_rollout_scratch", None) is None:
-                self._turn_rollout_scratch = self.turn_value_rollout_scratch()
-            scratch = self._turn_rollout_scratch
-        elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
-              or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
-            raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
-                             f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
-        self.handle.call("narde_turn_value_rollout_records", plies,
-                         *(ctypes.byref(m) if m is not None else None for m in structs),
-                         _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
-                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
-                         _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
-        self._keep = (net_white, net_black, structs, epsilon, tag, bufs, scratch)
-        return bufs
+        return self._value_rollout(self._kind.value_rollout, plies, (net_white, net_black), epsilon, tag, seed, bufs,
+                                   scratch)
 
     def net_table(self, nets, out=None):
         """The league launches' table of 1 .. 64 value_net.ValueMLPs on the
@@ -1167,7 +1186,7 @@ class VecNardeEnv:
             raise ValueError(f"a table holds 1 .. {_lib.LEAGUE_NETS_MAX} nets, not {len(nets)}")
         structs = (_lib.ValueMlp * len(nets))()
         for i, net in enumerate(nets):
-            if not hasattr(net, "struct"):
+            if not hasattr(net, "struct"):  # (the table's own wording, the device before the struct)
                 raise TypeError(f"nets[{i}] must be a gym_narde.value_net.ValueMLP")
             if net.l1.weight.device != self.device:
                 raise ValueError(f"nets[{i}] must live on the env's device")
@@ -1189,17 +1208,16 @@ class VecNardeEnv:
     def _league_args(self, table, white, black):
         """The league launches' checks of the table and the two index
         tensors: the number of nets."""
-        t, B = self.torch, self.num_envs
+        t, B, entry = self.torch, self.num_envs, _lib.league_table_bytes(1)
         if (not isinstance(table, t.Tensor) or table.dtype != t.uint8 or table.device != self.device
-                or not table.is_contiguous() or table.dim() != 1 or table.numel() % _lib.league_table_bytes(1)
-                or not 1 <= table.numel() // _lib.league_table_bytes(1) <= _lib.LEAGUE_NETS_MAX
-                or table.data_ptr() % 16):
+                or not table.is_contiguous() or table.dim() != 1 or table.numel() % entry
+                or not 1 <= table.numel() // entry <= _lib.LEAGUE_NETS_MAX or table.data_ptr() % 16):
             raise ValueError("table must be net_table()'s uint8 tensor on the env's device")
         for name, a in (("white", white), ("black", black)):
             if (not isinstance(a, t.Tensor) or a.dtype != t.int32 or a.device != self.device or not a.is_contiguous()
                     or tuple(a.shape) != (B,)):
                 raise ValueError(f"{name} must be a contiguous int32 device tensor of shape ({B},)")
-        return table.numel() // _lib.league_table_bytes(1)
+        return table.numel() // entry
 
     def value_rollout_league(self, plies, table, white, black, epsilon=None, tag=None, seed=0, bufs=None):
         """value_rollout() with a net per env and colour
@@ -1217,18 +1235,8 @@ class VecNardeEnv:
         white and black rewritten in place between replays."""
         if self.full:
             raise ValueError('value_rollout_league() is rules="ref2" only')
-        plies = int(plies)
-        if plies < 1:
-            raise ValueError("plies must be >= 1")
-        n_nets = self._league_args(table, white, black)
-        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, self.value_rollout_buffers,
-                                                      self._VALUE_ROLLOUT_BUFS)
-        self.handle.call("narde_value_rollout_league", plies, _lib.ptr(table), n_nets, _lib.ptr(white),
-                         _lib.ptr(black), _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
-                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._VALUE_ROLLOUT_BUFS),
-                         _lib.ptr(bufs.get("records")), self._s())
-        self._keep = (table, white, black, epsilon, tag, bufs)
-        return bufs
+        return self._value_rollout(self._kind.league, plies, (table, white, black), epsilon, tag, seed, bufs, None,
+                                   league=True)
 
     def turn_value_rollout_league(self, plies, table, white, black, epsilon=None, tag=None, seed=0, bufs=None,
                                   scratch=None):
@@ -1238,27 +1246,8 @@ class VecNardeEnv:
         the same bits whatever the number of pieces."""
         if not self.full:
             raise ValueError('turn_value_rollout_league() is rules="full4" only')
-        t = self.torch
-        plies = int(plies)
-        if plies < 1:
-            raise ValueError("plies must be >= 1")
-        n_nets = self._league_args(table, white, black)
-        epsilon, tag, bufs = self._value_rollout_bufs(plies, epsilon, tag, bufs, self.turn_value_rollout_buffers,
-                                                      self._TURN_VALUE_ROLLOUT_BUFS)
-        if scratch is None:
-            if getattr(self, "_turn_rollout_scratch", None) is None:
-                self._turn_rollout_scratch = self.turn_value_rollout_scratch()
-            scratch = self._turn_rollout_scratch
-        elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
-              or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
-            raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
-                             f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
-        self.handle.call("narde_turn_value_rollout_league", plies, _lib.ptr(table), n_nets, _lib.ptr(white),
-                         _lib.ptr(black), _lib.ptr(epsilon), int(seed) & (2 ** 64 - 1), _lib.ptr(tag),
-                         *(_lib.ptr(bufs.get(name)) for name, _, _ in self._TURN_VALUE_ROLLOUT_BUFS),
-                         _lib.ptr(scratch), int(scratch.numel()), _lib.ptr(bufs.get("records")), self._s())
-        self._keep = (table, white, black, epsilon, tag, bufs, scratch)
-        return bufs
+        return self._value_rollout(self._kind.league, plies, (table, white, black), epsilon, tag, seed, bufs, scratch,
+                                   league=True)
 
     def state_records(self, board, off, first_turn, player, t=0):
         """N positions (set_state()'s arrays, any N) as the 32-byte records
@@ -1309,41 +1298,26 @@ class VecNardeEnv:
         t = self.torch
         if isinstance(roots, dict):
             roots = self.state_records(roots["board"], roots["off"], roots["first_turn"], roots["player"])
-        if (not isinstance(roots, t.Tensor) or roots.dtype != t.int32 or roots.device != self.device
-                or not roots.is_contiguous() or roots.dim() != 2 or roots.shape[1] != 8 or roots.shape[0] < 1):
-            raise ValueError("roots must be a contiguous (N, 8) int32 device tensor of records, or a get_state() dict")
+        self._check_records(roots, "roots must be a contiguous (N, 8) int32 device tensor of records, or a get_state() "
+                                   "dict")
         N, trials, max_plies = int(roots.shape[0]), int(trials), int(max_plies)
         if trials < 1 or max_plies < 1:
             raise ValueError("trials and max_plies must be >= 1")
-        _, net_white, net_black, structs, _, _, _ = self._value_rollout_args(1, net_white, net_black, None, None, {},
-                                                                             None, ())
+        net_white, net_black, structs = self._net_pair(net_white, net_black)
         if out is None:
             mk = lambda on, dt: t.empty((N, trials), dtype=dt, device=self.device) if on else None  # noqa: E731
             out = PlayoutResult(t.empty((N, 4), dtype=t.int32, device=self.device), trials, mk(per_trial, t.int8),
                                 mk(per_trial, t.int32), mk(leaf, t.float32))
         elif tuple(out.sums.shape) != (N, 4) or out.trials != trials or out.sums.device != self.device:
             raise ValueError("out must be a PlayoutResult of the same roots and trials on this device")
-        args = [N, _lib.ptr(roots), trials, max_plies, *(ctypes.byref(m) if m is not None else None for m in structs),
-                int(seed) & (2 ** 64 - 1), int(id_base), _lib.PLAYOUT_COMMON_DICE if common_dice else 0,
-                _lib.ptr(out.sums), _lib.ptr(out.outcome), _lib.ptr(out.length), _lib.ptr(out.leaf)]
-        if self.full:
-            if scratch is None:
-                # min(N * trials, resident waves) pieces, kept on the env and grown when a call needs more
-                # (the occupancy query is made once: a later call, inside a graph capture too, makes no other
-                # call than the launch)
-                if getattr(self, "_playout_waves", None) is None:
-                    self._playout_waves = self.turn_value_rollout_waves()
-                need = _lib.turn_rollout_scratch_bytes(min(N * trials, self._playout_waves))
-                if getattr(self, "_playout_scratch", None) is None or self._playout_scratch.numel() < need:
-                    self._playout_scratch = t.empty(need, dtype=t.uint8, device=self.device)
-                scratch = self._playout_scratch
-            elif (scratch.dtype != t.uint8 or scratch.device != self.device or not scratch.is_contiguous()
-                  or scratch.numel() < _lib.turn_rollout_scratch_bytes(1)):
-                raise ValueError("scratch must be a contiguous uint8 device tensor of at least one piece "
-                                 f"({_lib.turn_rollout_scratch_bytes(1)} bytes; turn_value_rollout_scratch())")
-            self.handle.call("narde_turn_value_playout", *args, _lib.ptr(scratch), int(scratch.numel()), self._s())
-        else:
-            self.handle.call("narde_value_playout", *args, self._s())
+        tail = ()
+        if self._kind.turn_scratch:
+            scratch = self._turn_scratch(scratch, N * trials)
+            tail = (_lib.ptr(scratch), int(scratch.numel()))
+        self.handle.call(self._kind.playout, N, _lib.ptr(roots), trials, max_plies,
+                         *(ctypes.byref(m) if m is not None else None for m in structs), int(seed) & (2 ** 64 - 1),
+                         int(id_base), _lib.PLAYOUT_COMMON_DICE if common_dice else 0, _lib.ptr(out.sums),
+                         _lib.ptr(out.outcome), _lib.ptr(out.length), _lib.ptr(out.leaf), *tail, self._s())
         self._keep = (roots, net_white, net_black, structs, out, scratch)
         return out
 
@@ -1360,23 +1334,15 @@ class VecNardeEnv:
         Returns (target, weight), (N,) float32; out: an earlier pair to write
         into.  No synchronise."""
         t = self.torch
-        if isinstance(result, PlayoutResult):
-            sums, trials, lf = result.sums, result.trials, result.leaf
-        else:
-            sums, trials = result[0], int(result[1])
-            lf = result[2] if len(result) > 2 else None
-        if leaf and lf is None:
-            raise ValueError("leaf=True needs the playouts' leaf values (playout(leaf=True))")
-        lf = lf if leaf else None
+        sums, trials, lf = self._playout_sums(result, leaf)
         if (sums.dim() != 2 or sums.shape[1] != 4 or sums.shape[0] < 1 or sums.dtype != t.int32
                 or not sums.is_contiguous() or sums.device != self.device):
             raise ValueError("result must hold (N, 4) int32 sums on this device")
         N = int(sums.shape[0])
         if lf is not None and (tuple(lf.shape) != (N, trials) or lf.dtype != t.float32 or not lf.is_contiguous()):
             raise ValueError("leaf must be (N, trials) float32")
-        if roots is not None and (tuple(roots.shape) != (N, 8) or roots.dtype != t.int32 or not roots.is_contiguous()
-                                  or roots.device != self.device):
-            raise ValueError("roots must be the playouts' contiguous (N, 8) int32 records")
+        if roots is not None:
+            self._check_records(roots, "roots must be the playouts' contiguous (N, 8) int32 records", N, N)
         if out is not None:
             target, weight = out
         else:
@@ -1418,8 +1384,8 @@ class VecNardeEnv:
         bufargs = (_lib.ptr(bufs["obs"]), _lib.ptr(bufs["reward"]), _lib.ptr(bufs["terminated"]),
                    _lib.ptr(bufs["truncated"]), _lib.ptr(bufs["legal"]), _lib.ptr(bufs["actions"]))
         if events is None:
-            fn = self.handle.lib.narde_rollout_full if self.full else self.handle.lib.narde_rollout
-            name = "narde_rollout_full" if self.full else "narde_rollout"
+            name = self._kind.rollout
+            fn = getattr(self.handle.lib, name)
             args = (self.handle.h, int(plies)) + bufargs + (self._s(),)
         else:
             evs = []
